@@ -24,9 +24,21 @@ torch.distributed.run).
     all-gather of the lists + k-way merge/vote of the rank's query slice.
 `--dry-run` (CPU, gloo): plumbing check of the launcher and the
 decomposition only -- a plain torch brute force stands in for the HIP
-library and the line reports value null.
+library and the line reports value null (every leg's plumbing, with or
+without --full).
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline figure needs: set-up, W warm-up
+steps, K timed steps, the result line.  `--full` adds every other leg to the
+same line: the per-phase times (further untimed calls), the fp32 / fp16
+paths, cfg3_strong, the continuous-data leg, cfg5, the train-sharded leg,
+the native drop-in and MNIST-shape legs and the CPU baselines (each leg also
+has its own --no-... switch).
+`--dump-outputs DIR` writes what the last timed step handed its caller (the
+main leg's labels and flags) as DIR/<name>.npy in float32; the inputs are
+seeded, so two builds run with the same arguments are comparable output for
+output.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 """
 import argparse
 import glob
@@ -403,7 +415,7 @@ class CpuStandIn:
         return self.vote(lb.gather(1, o)[:, :k], k)
 
 
-def timed_run(kd, clf, step, steps, warmup, sync, dev, precision=None):
+def timed_run(kd, clf, step, steps, warmup, sync, dev, precision=None, phases=True, after=None):
     """W untimed steps, then exactly K timed steps bracketed by barrier + sync
     (max over ranks); the candidate kernel's HIP-event times and the rescan
     counts of the K timed calls are read back only after the timed region.
@@ -411,7 +423,9 @@ def timed_run(kd, clf, step, steps, warmup, sync, dev, precision=None):
     (each event record holds the stream ~6 us: 5 per call cost ~2 % of a
     cfg2 step, profiles/ab_log.md r5u); the other phases' times (prep,
     re-rank, rescan) come from up to 5 further, untimed calls with every
-    phase's events."""
+    phase's events (phases=False: no further calls, those times are None).
+    after(): called right after the timed region, before any further call;
+    its return value is the result's "snap" (the last timed step's outputs)."""
     if precision is not None:
         clf.set_precision(precision)
     for _ in range(warmup):
@@ -422,19 +436,24 @@ def timed_run(kd, clf, step, steps, warmup, sync, dev, precision=None):
     clf.rescan_totals(reset=True)
     clf.tie_totals(reset=True)
     el = kd.timed(step, steps, 0, sync, dev)
+    snap = after() if after is not None else None
     ms, calls = clf.timing_totals(reset=True)
     resc = clf.rescan_totals(reset=True)
     ties = clf.tie_totals(reset=True)
     calls = max(1, calls)
-    clf.set_timing(True)
-    for _ in range(min(steps, 5)):
-        step()
-    sync()
-    ph, pcalls = clf.timing_totals(reset=True)
-    pcalls = max(1, pcalls)
-    clf.set_timing(True, kernel_only=True)  # (the mode the timed calls ran in)
-    return dict(el=el, t_cand=ms[1] / calls * 1e-3, rr=ph[2] / pcalls, rescan_ms=ph[3] / pcalls,
-                prep_ms=ph[0] / pcalls, phase_calls=pcalls, calls=calls, resc=resc[0],
+    rr = rescan_ms = prep_ms = None
+    pcalls = 0
+    if phases:
+        clf.set_timing(True)
+        for _ in range(min(steps, 5)):
+            step()
+        sync()
+        ph, pcalls = clf.timing_totals(reset=True)
+        pcalls = max(1, pcalls)
+        clf.set_timing(True, kernel_only=True)  # (the mode the timed calls ran in)
+        rr, rescan_ms, prep_ms = ph[2] / pcalls, ph[3] / pcalls, ph[0] / pcalls
+    return dict(el=el, snap=snap, t_cand=ms[1] / calls * 1e-3, rr=rr, rescan_ms=rescan_ms,
+                prep_ms=prep_ms, phase_calls=pcalls, calls=calls, resc=resc[0],
                 full_scans=resc[1],
                 tie_reordered=ties,
                 path=clf.last_candidate_path(), geom=clf.last_geometry(),
@@ -871,6 +890,31 @@ def cfg5_leg(args, kd, knn, dev, sync, stream):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, world, rank, **arrays):
+    """--dump-outputs: the arrays the timed path's last step handed its
+    caller, one DIR/<name>.npy each (<name>_rank<r>.npy with more than one
+    rank) in float32: labels and flag bits are small integers, exact there.
+    An array too long for its share of DUMP_LIMIT_BYTES is written as a
+    fixed, seeded sample of its rows (ascending row order); a single row
+    beyond that share is an error."""
+    os.makedirs(path, exist_ok=True)
+    elems_max = DUMP_LIMIT_BYTES // 4 // max(1, world) // len(arrays)  # float32 elements per array
+    for name, t in arrays.items():
+        a = t.detach().to("cpu").numpy().astype(np.float32)
+        per_row = max(1, int(np.prod(a.shape[1:])))
+        if per_row > elems_max:
+            raise ValueError("--dump-outputs: one row of %s (%d values) exceeds its share of "
+                             "the %d-byte limit" % (name, per_row, DUMP_LIMIT_BYTES))
+        if a.shape[0] * per_row > elems_max:
+            keep = np.random.default_rng(20240).choice(a.shape[0], elems_max // per_row,
+                                                       replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(path, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), a)
+
+
 def main():
     """Runs the bench; any failure on any rank exits non-zero naming the rank
     and the phase it was in (a hung collective fails after the process
@@ -929,6 +973,12 @@ def _main():
                          "e.g. qres=1 for the query-resident d > 256 kernel); repeatable")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo plumbing check with a torch stand-in (no measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (per-phase times, fp32 / fp16 paths, cfg3, "
+                         "continuous data, cfg5, train-sharded, drop-in, MNIST shape, CPU "
+                         "baselines); a plain run times the main leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (labels, flags) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -944,7 +994,7 @@ def _main():
         return dry_run(args, kd, world, rank)
     # the native drop-in over all N GPUs, as a child process, before this
     # process (or any other rank) touches a GPU
-    dropin = None if args.no_dropin or args.mode != "query" else dropin_phase(
+    dropin = None if not args.full or args.no_dropin or args.mode != "query" else dropin_phase(
         world, rank, mnist=not args.no_mnist)
 
     phase("device %d setup" % local)
@@ -1008,7 +1058,11 @@ def _main():
         prec_main = {"auto": knn.PRECISION_AUTO, "fp32": knn.PRECISION_FP32,
                      "fp16": knn.PRECISION_FP16}[args.precision]
         phase("main leg (query-sharded, %d queries per rank)" % m)
-        main_r = timed_run(kd, clf, step, args.steps, args.warmup, sync, dev, prec_main)
+        main_r = timed_run(kd, clf, step, args.steps, args.warmup, sync, dev, prec_main,
+                           phases=args.full, after=lambda: (out_lab.clone(), out_flags.clone()))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, world, rank, labels=main_r["snap"][0],
+                         flags=main_r["snap"][1])
         clf.set_precision(knn.PRECISION_AUTO)
         log("default path done: %.3f ms/step" % (main_r["el"] / args.steps * 1e3))
         labels_auto = out_lab.clone()
@@ -1024,7 +1078,7 @@ def _main():
         tie_vote = int(sum(pr["tie_vote_queries"]))
         extra["tie_vote_queries"] = tie_vote
         fp32_r = same = fp16_r = same16 = None
-        if not args.no_fp32_path and world == 1:
+        if args.full and not args.no_fp32_path and world == 1:
             fp32_r = timed_run(kd, clf, step, max(3, args.steps // 2), 1, sync, dev,
                                knn.PRECISION_FP32)
             same = bool(torch.equal(labels_auto, out_lab))
@@ -1043,7 +1097,7 @@ def _main():
         parallelism = "query-sharded dp%d" % world
         scaling = "weak"
 
-        if args.cfg3_queries > 0 and d == 128 and n == 1_000_000:
+        if args.full and args.cfg3_queries > 0 and d == 128 and n == 1_000_000:
             # configs[2]: a fixed query count split over the ranks (strong scaling)
             M = args.cfg3_queries
             q0, q1 = kd.shard_range(M, world, rank)
@@ -1084,7 +1138,7 @@ def _main():
                 log("cfg3 strong leg: %.1f ms/step" % (r3["el"] / s3 * 1e3))
                 del Q3, lab3, flg3
 
-        if not args.no_continuous and args.data == "grid" and world == 1:
+        if args.full and not args.no_continuous and args.data == "grid" and world == 1:
             # the same workload on continuous (min-max normalised, off-grid) data
             Xc, labc, Qc, _ = synth(n, m, d, C, 4242, 2424, dev, data="continuous")
             clf.set_train_device(Xc.data_ptr(), labc.data_ptr(), n, d, C, keep=(Xc, labc))
@@ -1120,7 +1174,7 @@ def _main():
             log("continuous-data leg: %.3f ms/step, %d rescans" % (rc["el"] / sc * 1e3, rc["resc"]))
             del Xc, labc, Qc
             clf.set_train_device(X.data_ptr(), lab.data_ptr(), n, d, C, keep=(X, lab))
-        if not args.no_cfg5 and world == 1 and (n, d, k) == (1_000_000, 128, 10):
+        if args.full and not args.no_cfg5 and world == 1 and (n, d, k) == (1_000_000, 128, 10):
             log("cfg5 leg (1M x 10k, d=960, k=100) ...")
             extra["cfg5"] = cfg5_leg(args, kd, knn, dev, sync, stream)
             log("cfg5 leg: %.2f ms/step" % extra["cfg5"]["ms_per_step"])
@@ -1163,7 +1217,12 @@ def _main():
 
         n_rank, m_rank = r1 - r0, m
         flops = 2.0 * (r1 - r0) * d * m
-        main_r = timed_run(kd, clf, step, args.steps, args.warmup, sync, dev, knn.PRECISION_AUTO)
+        main_r = timed_run(kd, clf, step, args.steps, args.warmup, sync, dev, knn.PRECISION_AUTO,
+                           phases=args.full,
+                           after=lambda: (out_lab[:q1 - q0].clone(), out_flg[:q1 - q0].clone()))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, world, rank, labels=main_r["snap"][0],
+                         flags=main_r["snap"][1])
         fp32_r, same, fp16_r, same16 = None, None, None, None
         total_q = m * args.steps
         workload = ("cfg4-shape: %d train (sharded) x %d queries, d=%d, k=%d, L2, %d classes"
@@ -1172,7 +1231,7 @@ def _main():
         scaling = "strong"
 
     ts = None
-    if args.mode == "query" and not args.no_train_sharded:
+    if args.full and args.mode == "query" and not args.no_train_sharded:
         log("train-sharded leg: %d rows over %d rank(s) ..." % (args.ts_n_train, world))
         phase("train-sharded leg (%d rows over %d ranks)" % (args.ts_n_train, world))
         ts = train_sharded_leg(args, kd, knn, world, rank, local, dev, sync)
@@ -1233,9 +1292,11 @@ def _main():
                      "rescan_ms": main_r["rescan_ms"], "prep_ms": main_r["prep_ms"],
                      "timed_launches": main_r["calls"],
                      "phase_ms_source": ("kernel_ms: HIP events around the candidate kernel of "
-                                         "the %d timed calls; prep/rerank/rescan_ms: %d further "
-                                         "untimed calls after the timed region with every "
-                                         "phase's events" % (main_r["calls"], main_r["phase_calls"])),
+                                         "the %d timed calls; prep/rerank/rescan_ms: %s"
+                                         % (main_r["calls"],
+                                            "%d further untimed calls after the timed region with "
+                                            "every phase's events" % main_r["phase_calls"]
+                                            if args.full else "not measured (--full)")),
                      "algorithmic_flops_per_launch": flops,
                      "mfma_flops_per_algorithmic_flop": mfma_mult,
                      "frac_of_issued_mfma": achieved * mfma_mult / peak},
@@ -1249,7 +1310,7 @@ def _main():
         result["group_workload"] = dropin.get("workload")
     if ts is not None:
         result["train_sharded"] = ts
-    if args.mode == "query":
+    if args.full and args.mode == "query":  # (notes on legs that only a --full line carries)
         result["scaling_note"] = (
             "value is weak scaling (10k queries per GPU); north_star's >=7x-at-8-GPUs claim "
             "rests on cfg3_strong (a fixed 1M queries split over the ranks) and the "
@@ -1277,7 +1338,7 @@ def _main():
             "peak": peak_of(fp16_r["path"]), "frac": a16 / peak_of(fp16_r["path"]),
             "candidate_path": fp16_r["path"], "rescanned_queries": fp16_r["resc"],
             "labels_equal_default_path": same16}
-    if rank == 0 and world == 1 and args.mode == "query" and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.mode == "query" and not args.no_cpu_baseline:
         log("cpu baseline (oracle port) ...")
         port = cpu_baseline(X, lab, Q, k, C, labels_auto.cpu().numpy(), budget_s=6.0)
         result["cpu_baseline"] = port
@@ -1374,6 +1435,8 @@ def dry_run(args, kd, world, rank):
         out["lab"] = clf.classify(Q[q0:q1], k)
 
     el = kd.timed(step, args.steps, args.warmup, lambda: None, None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, labels=out["lab"])
     labels = kd.gather_slices(out["lab"], m * world)
     # the train-sharded decomposition: rank r's rows only, one all-gather of
     # the packed lists, merge + vote of the rank's query slice

@@ -259,6 +259,48 @@ def test_bench_launches_its_own_ranks():
     assert two["train_sharded"]["labels_sha1"] == one48["train_sharded"]["labels_sha1"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's labels as float32 .npy:
+    the very labels whose sha1 the line reports, and only that file."""
+    import hashlib
+    out = tmp_path / "dump"
+    line = _bench_line(["--dry-run", "--n-train", "500", "--dim", "8", "--queries", "37",
+                        "--steps", "2", "--warmup", "0", "--gpus", "1",
+                        "--dump-outputs", str(out)])
+    assert sorted(p.name for p in out.iterdir()) == ["labels.npy"]
+    lab = np.load(out / "labels.npy")
+    assert lab.dtype == np.float32 and lab.shape == (37,)
+    assert hashlib.sha1(lab.astype(np.int32).tobytes()).hexdigest() == line["labels_sha1"]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+
+
+def test_dump_outputs_sampling_and_rank_names(tmp_path, monkeypatch):
+    """bench.dump_outputs past its size limit: a fixed, seeded sample of whole
+    rows in ascending order, the same on every call; one file per rank; an
+    array within its share is written whole; a row beyond it is an error."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 2 * 2 * 100)  # 100 values per array
+    lab = torch.arange(1000, dtype=torch.int32) * 3
+    nb = torch.arange(3000, dtype=torch.int64).reshape(1000, 3)
+    small = torch.arange(100, dtype=torch.int32)
+    a, b = tmp_path / "a", tmp_path / "b"
+    for dst in (a, b):
+        bench.dump_outputs(str(dst), 2, 1, labels=lab, nb=nb)
+    assert sorted(p.name for p in a.iterdir()) == ["labels_rank1.npy", "nb_rank1.npy"]
+    la, na = np.load(a / "labels_rank1.npy"), np.load(a / "nb_rank1.npy")
+    assert la.dtype == np.float32 and la.shape == (100,) and na.shape == (33, 3)
+    assert (np.diff(la) > 0).all() and (la % 3 == 0).all() and la.max() <= 2997
+    assert (np.diff(na[:, 0]) > 0).all() and (na[:, 0] % 3 == 0).all()
+    assert (na[:, 1] == na[:, 0] + 1).all() and (na[:, 2] == na[:, 0] + 2).all()
+    assert np.array_equal(la, np.load(b / "labels_rank1.npy"))
+    assert np.array_equal(na, np.load(b / "nb_rank1.npy"))
+    c = tmp_path / "c"
+    bench.dump_outputs(str(c), 2, 0, labels=small, flags=small)
+    assert np.array_equal(np.load(c / "labels_rank0.npy"), np.arange(100, dtype=np.float32))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(c), 2, 0, wide=torch.zeros((2, 500)))
+
+
 def test_bench_failure_names_rank_and_phase():
     """A failing rank exits non-zero and names itself and the phase it was in
     (a negative --n-train makes the dry run's data generation fail)."""

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
-B="--steps 30 --warmup 5 --no-cpu-baseline --no-fp32-path --no-continuous --no-dropin --no-train-sharded --no-cfg5 --cfg3-queries 0 $BENCH_ARGS"
+B="--full --steps 30 --warmup 5 --no-cpu-baseline --no-fp32-path --no-continuous --no-dropin --no-train-sharded --no-cfg5 --cfg3-queries 0 $BENCH_ARGS"
 # parity gate per library before any timing (tests/test_gpu_gate.py: the
 # oracle on 8 queries + brute-force optimality on 256 at cfg2)
 for v in $AB_VARIANTS; do

@@ -22,26 +22,26 @@ for s in "$@"; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1000 python -u -m pytest tests -m gpu -q -p no:cacheprovider -x --timeout 300 --timeout-method thread ;;
     testsall) step testsall 900 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 2 ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 2 ;;
     prof)
       export TMPDIR=/tmp
       step prof 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG" \
         -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 5 --warmup 1 \
-        --no-cpu-baseline ;;
+        --full --no-cpu-baseline ;;
     pmc)
       export TMPDIR=/tmp
       step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$GRAFT_REPO_ROOT/gpurun_out/pmc_fetch_$TAG" \
         -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 2 --warmup 1 \
-        --no-cpu-baseline
+        --full --no-cpu-baseline
       step pmc_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$GRAFT_REPO_ROOT/gpurun_out/pmc_write_$TAG" \
         -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 2 --warmup 1 \
-        --no-cpu-baseline ;;
+        --full --no-cpu-baseline ;;
     pmcsq)
       export TMPDIR=/tmp
       step pmc_sq 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU \
         SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace \
         -d "$GRAFT_REPO_ROOT/gpurun_out/pmc_sq_$TAG" -o run --output-format csv -- \
-        python3 "$GRAFT_REPO_ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline ;;
+        python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ;;
     tune) step tune 600 python tools/tune.py ${TUNE_ARGS:-} ;;
     *) nc=$((nc+1)); step custom$nc 600 bash -c "$s" ;;
   esac

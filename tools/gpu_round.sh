@@ -125,14 +125,14 @@ if [ -n "$BENCH_SETS" ]; then
   done
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 ${BENCH_LIMIT:-400} python3 -u bench.py --steps 20 --warmup 5 ${BENCH_ARGS} \
+  timeout -k 10 ${BENCH_LIMIT:-400} python3 -u bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS} \
       > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log
   rc=$?; echo "bench rc=$rc"; tail -c 600 $O/${TAG}_bench.json
   [ $rc = 0 ] || exit $rc
 fi
 if [ -n "$PROF" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof -o prof -- \
-      python3 -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-path --no-continuous --no-dropin --no-train-sharded --cfg3-queries 0 > $O/${TAG}_prof.log 2>&1
+      python3 -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-path --no-continuous --no-dropin --no-train-sharded --cfg3-queries 0 > $O/${TAG}_prof.log 2>&1
   rc=$?; echo "prof rc=$rc"
   [ $rc = 0 ] || exit $rc
 fi
