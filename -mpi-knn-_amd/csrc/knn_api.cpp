@@ -816,7 +816,7 @@ static void auto_check(knn_ctx* ctx) {
 // (Partial lists stay ordered by (dist, global idx): the reference's order
 // over the whole train set is restored after the merge, knn_tie_resolve_device.)
 static int tie_mask_of(const knn_ctx* ctx, const Sink& sink) {
-  if (sink.mode != MODE_SINGLE) return 0;
+  if (sink.mode != MODE_SINGLE || sink.tie_defer) return 0;
   return ctx->tune_ties;
 }
 
@@ -1277,6 +1277,37 @@ static int run_large_k(knn_ctx* ctx, const double* dQ, int64_t m, int W, int met
   return KNN_OK;
 }
 
+// K sweep (knn_sweep.hip): ks is a host array in any order, duplicates allowed.
+int knn_sweep_check_ks(const int32_t* ks, int32_t nk, int64_t n, int32_t* kmax) {
+  if (nk < 1 || nk > 4096)
+    return knn_fail(KNN_ERR_ARG, "nk = " + std::to_string(nk) + " must be in [1, 4096]");
+  if (!ks) return knn_fail(KNN_ERR_ARG, "null ks");
+  int32_t mx = 0;
+  for (int32_t i = 0; i < nk; i++) {
+    if (ks[i] < 0)
+      return knn_fail(KNN_ERR_ARG, "ks[" + std::to_string(i) + "] = " + std::to_string(ks[i]) +
+                                       " must be >= 0");
+    if (ks[i] > n)
+      return knn_fail(KNN_ERR_ARG, "ks[" + std::to_string(i) + "] = " + std::to_string(ks[i]) +
+                                       " exceeds " + std::to_string(n) +
+                                       " (the rows available to vote over)");
+    mx = std::max(mx, ks[i]);
+  }
+  *kmax = mx;
+  return KNN_OK;
+}
+
+// the list of K on the device (a copy from pageable host memory: staged by
+// the runtime before the call returns) and the zeroed correct counts
+static int sweep_upload(knn_ctx* ctx, const int32_t* ks, int32_t nk, int64_t* d_correct,
+                        hipStream_t s) {
+  int rc;
+  if ((rc = ctx->sw_ks.ensure((size_t)nk * sizeof(int32_t)))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->sw_ks.p, ks, (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (d_correct) HIP_TRY(hipMemsetAsync(d_correct, 0, (size_t)nk * sizeof(int64_t), s));
+  return KNN_OK;
+}
+
 static int check_query_args(knn_ctx* ctx, int64_t m, int32_t k, int32_t metric) {
   if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "classify before set_train");
   if (m < 0) return knn_fail(KNN_ERR_ARG, "m must be >= 0");
@@ -1351,6 +1382,154 @@ int knn_classify(knn_ctx* ctx, const double* Q, int64_t m, int32_t k, int32_t me
                            hipMemcpyDeviceToHost, s));
   if (out_dist && k > 0)
     HIP_TRY(hipMemcpyAsync(out_dist, ctx->o_dist.p, (size_t)m * k * sizeof(double),
+                           hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return KNN_OK;
+}
+
+int knn_vote_sweep_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_t kmax,
+                          const int32_t* d_lab, int64_t idx_base, const int32_t* ks, int32_t nk,
+                          int32_t* d_labels, const int32_t* d_truth, int64_t* d_correct,
+                          void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  int32_t top = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, kmax, &top))) return rc;
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (kmax > 0 && (!d_idx || !d_lab)) return knn_fail(KNN_ERR_ARG, "null neighbour rows / labels");
+  launch_sweep_vote(d_idx, m, kmax, d_lab, idx_base, (const int*)ctx->sw_ks.p, nk, d_labels,
+                    d_truth, (unsigned long long*)d_correct, ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+int knn_classify_sweep_device(knn_ctx* ctx, const double* dQ, int64_t m, const int32_t* ks,
+                              int32_t nk, int32_t metric, int32_t* d_labels,
+                              const int32_t* d_truth, int64_t* d_correct, int64_t* d_idx,
+                              double* d_dist, int32_t* d_flags, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const TrainDev& t = ctx->train;
+  const int* dks = (const int*)ctx->sw_ks.p;
+  if (kmax == 0) {  // every K is 0: max_label stays -1 (cpp:324)
+    launch_sweep_vote(nullptr, m, 0, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
+                      (unsigned long long*)d_correct, ctx->cu_count, s);
+    if (d_flags) launch_fill_i32(d_flags, m, 0, s);
+    HIP_TRY(hipGetLastError());
+    return KNN_OK;
+  }
+  // one search at kmax into rows the sweep always keeps (idx, dist, flags);
+  // the search neither queues ties nor runs the reference-order pass
+  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
+  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
+  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  Sink sink{};
+  sink.mode = MODE_SINGLE;
+  sink.k = kmax;
+  sink.idx_off = ctx->idx_off;
+  sink.labels = (int32_t*)ctx->sw_lab.p;
+  sink.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
+  sink.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
+  sink.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
+  sink.tie_defer = 1;
+  const int W = (int)std::min<int64_t>((int64_t)kmax + 1, t.n);
+  rc = kmax > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
+                    : knn_run_search(ctx, dQ, m, W, metric, sink, s);
+  if (rc) return rc;
+  // queries whose label at some K of the list the reference's tie order could
+  // change -> the tie queue -> the reference-order pass over the whole top kmax
+  if (ctx->tune_ties) {
+    const int64_t tie_per = tie_scratch_bytes(t.n, ctx->class_cnt);
+    const int tie_nwg = tie_workgroups(ctx, tie_per);
+    if ((rc = ctx->tie_q.ensure((size_t)m * sizeof(int) + 16))) return rc;
+    if ((rc = ctx->tie_ws.ensure((size_t)(tie_per * tie_nwg)))) return rc;
+    if ((rc = ctx->rescan_cnt.ensure(4 * sizeof(int)))) return rc;
+    sink.tie_mode = ctx->tune_ties;
+    sink.tie_q = (int*)ctx->tie_q.p;
+    sink.tie_cnt = (int*)ctx->rescan_cnt.p + 2;
+    HIP_TRY(hipMemsetAsync(sink.tie_cnt, 0, sizeof(int), s));
+    launch_sweep_tie_scan(sink.dist, sink.idx, sink.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
+                          sink.tie_mode, sink.tie_q, sink.tie_cnt, ctx->cu_count, s);
+    launch_tie_order(metric, t, dQ, sink.tie_q, sink.tie_cnt, ctx->class_cnt,
+                     (unsigned char*)ctx->tie_ws.p, tie_per, tie_nwg, sink,
+                     (unsigned long long*)ctx->totals.p + 2, s);
+  }
+  launch_sweep_vote(sink.idx, m, kmax, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
+                    (unsigned long long*)d_correct, ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+  return KNN_OK;
+}
+
+int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks, int32_t nk,
+                       int32_t metric, int32_t* out_labels, const int32_t* truth,
+                       int64_t* out_correct, int64_t* out_idx, double* out_dist,
+                       int32_t* out_flags) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
+  if ((truth != nullptr) != (out_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "truth and out_correct go together (both or neither)");
+  if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  if (m > 0 && !Q) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const int d = ctx->train.d;
+  const size_t mk = (size_t)m * std::max(kmax, 1);
+  if ((rc = ctx->Q64.ensure((size_t)m * d * sizeof(double)))) return rc;
+  if ((rc = ctx->sw_out.ensure((size_t)m * nk * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->o_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (truth && (rc = ctx->sw_truth.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (truth && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_idx && (rc = ctx->o_idx.ensure(mk * sizeof(int64_t)))) return rc;
+  if (out_dist && (rc = ctx->o_dist.ensure(mk * sizeof(double)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (m > 0) {
+    HIP_TRY(hipMemcpyAsync(ctx->Q64.p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, s));
+    if (truth)
+      HIP_TRY(hipMemcpyAsync(ctx->sw_truth.p, truth, (size_t)m * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s));
+  }
+  rc = knn_classify_sweep_device(ctx, (const double*)ctx->Q64.p, m, ks, nk, metric,
+                                 (int32_t*)ctx->sw_out.p,
+                                 truth ? (const int32_t*)ctx->sw_truth.p : nullptr,
+                                 truth ? (int64_t*)ctx->sw_corr.p : nullptr,
+                                 out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
+                                 out_dist ? (double*)ctx->o_dist.p : nullptr,
+                                 (int32_t*)ctx->o_flags.p, s);
+  if (rc) return rc;
+  if (m > 0)
+    HIP_TRY(hipMemcpyAsync(out_labels, ctx->sw_out.p, (size_t)m * nk * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_correct)
+    HIP_TRY(hipMemcpyAsync(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_flags && m > 0)
+    HIP_TRY(hipMemcpyAsync(out_flags, ctx->o_flags.p, (size_t)m * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_idx && m > 0 && kmax > 0)
+    HIP_TRY(hipMemcpyAsync(out_idx, ctx->o_idx.p, (size_t)m * kmax * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_dist && m > 0 && kmax > 0)
+    HIP_TRY(hipMemcpyAsync(out_dist, ctx->o_dist.p, (size_t)m * kmax * sizeof(double),
                            hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return KNN_OK;

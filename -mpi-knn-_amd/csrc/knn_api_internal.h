@@ -119,6 +119,9 @@ struct knn_ctx {
   DevBuf mrg;
   // reference tie order pass: queued queries, per-workgroup scratch
   DevBuf tie_q, tie_ws;
+  // K sweep: the list of K, the search's label / idx / dist / flags at kmax,
+  // host-API staging of labels [nk][m], truth [m] and correct counts [nk]
+  DevBuf sw_ks, sw_lab, sw_idx, sw_dist, sw_flags, sw_out, sw_truth, sw_corr;
   // host-API outputs
   DevBuf o_lab, o_idx, o_dist, o_flags;
   // normalisation: per-thread partial max/min, bounds, host-API staging
@@ -130,10 +133,14 @@ struct knn_ctx {
             &slow_q,  &totals,  &lk, &mrg, &tie_q, &tie_ws, &o_lab, &o_idx, &o_dist, &o_flags, &nrm_part, &nrm_mm, &nrm_X,
             &rescan_mask, &rescan_nkeep, &rescan_qc8, &rescan_t8, &smp_x64, &smp_xl2, &smp_img, &smp_scr, &smp_v, &smp_i,
             &ord_cent, &ord_cnorm, &ord_img, &ord_rank, &ord_rstart, &ord_perm, &ord_ipos, &ord_key, &ord_bcnt, &ord_tot,
-            &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0};
+            &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
+            &sw_out, &sw_truth, &sw_corr};
   }
 };
 
 int knn_fail(int code, const std::string& msg);
+// K sweep argument check shared with knn_group.cpp: 1 <= nk <= 4096 and 0 <=
+// ks[i] <= n (KNN_ERR_ARG naming the offending entry); *kmax = max K
+int knn_sweep_check_ks(const int32_t* ks, int32_t nk, int64_t n, int32_t* kmax);
 int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                    const knnk::Sink& sink, hipStream_t s);

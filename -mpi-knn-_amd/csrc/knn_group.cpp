@@ -49,6 +49,7 @@ struct knn_group {
   std::vector<DevBuf> Q, olab, oidx, odist, oflags;
   std::vector<DevBuf> pk, gk;                  // train-sharded packed partial / gathered lists
   std::vector<DevBuf> tq, tcnt, tsel, trow, tsend, trecv;  // reference tie order exchange
+  std::vector<DevBuf> slab, struth, scorr, sks;  // K sweep: labels [nk][mi], truth, correct counts, ks
   std::vector<DevBuf> nX, nmm;                 // normalisation shards / per-dim bounds
   std::vector<hipEvent_t> ev0, ev1;            // per device: around the last call's device work
   std::vector<hipEvent_t> evx;                 // loopback: cross-rank stream ordering
@@ -343,7 +344,7 @@ int knn_group_create(knn_group** out, int ndev, const int* devs, int mode) {
   }
   for (auto* v : {&g->X, &g->lab, &g->labA, &g->Q, &g->olab, &g->oidx, &g->odist, &g->oflags,
                   &g->pk, &g->gk, &g->tq, &g->tcnt, &g->tsel, &g->trow, &g->tsend, &g->trecv,
-                  &g->nX, &g->nmm})
+                  &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks})
     v->resize(ndev);
   g->ev0.assign(ndev, nullptr);
   g->ev1.assign(ndev, nullptr);
@@ -389,7 +390,7 @@ int knn_group_destroy(knn_group* g) {
     }
     for (auto* v : {&g->X, &g->lab, &g->labA, &g->Q, &g->olab, &g->oidx, &g->odist, &g->oflags,
                     &g->pk, &g->gk, &g->tq, &g->tcnt, &g->tsel, &g->trow, &g->tsend, &g->trecv,
-                    &g->nX, &g->nmm})
+                    &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks})
       if (i < (int)v->size()) (*v)[i].release();
     for (auto* ev : {&g->ev0, &g->ev1, &g->evx})
       if (i < (int)ev->size() && (*ev)[i]) (void)hipEventDestroy((*ev)[i]);
@@ -581,6 +582,89 @@ static int resolve_ties(knn_group* g, int64_t m, int k, int metric) {
   return KNN_OK;
 }
 
+// Train-sharded search of one call: queries to every rank, each rank's exact
+// local top-w, the all-gather of the packed lists and each rank's k-way merge
+// + vote of its query slice into olab / oidx / odist / oflags (k per row).
+// ties: MergeTies::mode of the merges (queries queued in tq / tcnt); 0 for
+// the K sweep, whose own scan fills the queues afterwards.
+static int sharded_search(knn_group* g, const double* Q, int64_t m, int k, int metric, int ties) {
+  const int G = g->ndev;
+  const int d = g->d;
+  int rc;
+  auto slice = [&](int i, int64_t& q0, int64_t& mi) {
+    q0 = m * i / G;
+    mi = m * (i + 1) / G - q0;
+  };
+  // each GPU's exact local top-w (w <= its shard: padded with idx -1); any
+  // K <= N_train like cpp:328 (unions beyond 4096 entries: the rank merge)
+  const int w = (int)std::min<int64_t>((int64_t)k + 1, g->n);
+  const int64_t PB = knnk::packed_part_bytes(m, w);
+  for (int i = 0; i < G; i++) {
+    int64_t q0, mi;
+    slice(i, q0, mi);
+    HIP_G(hipSetDevice(g->devs[i]));
+    if ((rc = g->Q[i].ensure((size_t)m * d * sizeof(double)))) return rc;
+    // this GPU's lists packed [dist | idx | label] (one all-gather per step)
+    if ((rc = g->pk[i].ensure((size_t)PB))) return rc;
+    if (g->transport != XPORT_NONE && (rc = g->gk[i].ensure((size_t)G * PB))) return rc;
+    if ((rc = g->olab[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int32_t)))) return rc;
+    if ((rc = g->oflags[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int32_t)))) return rc;
+    if ((rc = g->oidx[i].ensure((size_t)std::max<int64_t>(mi, 1) * k * sizeof(int64_t)))) return rc;
+    if ((rc = g->odist[i].ensure((size_t)std::max<int64_t>(mi, 1) * k * sizeof(double)))) return rc;
+    if ((rc = g->tq[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int)))) return rc;
+    if ((rc = g->tcnt[i].ensure(sizeof(int)))) return rc;
+    if (const int64_t sb = knnk::merge_scratch_bytes(G, w, k, mi))
+      if ((rc = g->ctx[i]->mrg.ensure((size_t)sb))) return rc;
+  }
+  // queries to the first GPU, broadcast to the rest
+  HIP_G(hipSetDevice(g->devs[0]));
+  HIP_G(hipMemcpyAsync(g->Q[0].p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice,
+                       g->ctx[0]->stream));
+  for (int i = 0; i < G; i++) {
+    HIP_G(hipSetDevice(g->devs[i]));
+    HIP_G(hipEventRecord(g->ev0[i], g->ctx[i]->stream));
+  }
+  std::vector<void*> qb(G), sp(G), rp(G);
+  for (int i = 0; i < G; i++) {
+    qb[i] = g->Q[i].p;
+    sp[i] = g->pk[i].p;
+    rp[i] = g->gk[i].p;
+  }
+  if ((rc = coll_bcast(g, qb, (size_t)m * d, ncclFloat64, 8, 0))) return rc;
+  for (int i = 0; i < G; i++) {
+    HIP_G(hipSetDevice(g->devs[i]));
+    unsigned char* pb = (unsigned char*)g->pk[i].p;
+    if ((rc = knn_search_partial_device(g->ctx[i], (const double*)g->Q[i].p, m, w, metric,
+                                        (double*)pb, (int64_t*)(pb + 8 * m * w),
+                                        (int32_t*)(pb + 16 * m * w), nullptr)))
+      return rc;
+  }
+  // one all-gather of the packed lists (≙ the reference's MPI_Gather, cpp:340)
+  if ((rc = coll_allgather(g, sp, rp, (size_t)PB))) return rc;
+  for (int i = 0; i < G; i++) {
+    int64_t q0, mi;
+    slice(i, q0, mi);
+    HIP_G(hipSetDevice(g->devs[i]));
+    hipStream_t s = g->ctx[i]->stream;
+    if (mi > 0) {
+      const double* sk = (const double*)(g->transport != XPORT_NONE ? g->gk[i].p : g->pk[i].p);
+      knnk::MergeTies mt;
+      mt.mode = ties;
+      mt.q = ties ? (int*)g->tq[i].p : nullptr;
+      mt.cnt = (int*)g->tcnt[i].p;
+      HIP_G(hipMemsetAsync(mt.cnt, 0, sizeof(int), s));
+      knnk::launch_merge_vote_partials(sk, nullptr, nullptr, G, m, w, k, (int32_t*)g->olab[i].p,
+                                       (int64_t*)g->oidx[i].p, (double*)g->odist[i].p,
+                                       (int32_t*)g->oflags[i].p, s, q0, mi, PB, g->ctx[i]->mrg.p,
+                                       mt);
+      HIP_G(hipGetLastError());
+    } else {
+      HIP_G(hipMemsetAsync(g->tcnt[i].p, 0, sizeof(int), s));
+    }
+  }
+  return KNN_OK;
+}
+
 extern "C" {
 
 int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int32_t metric,
@@ -676,78 +760,159 @@ int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int3
       for (int64_t q = 0; q < m; q++) out_flags[q] = 0;
     return KNN_OK;
   }
-  // each GPU's exact local top-w (w <= its shard: padded with idx -1); any
-  // K <= N_train like cpp:328 (unions beyond 4096 entries: the rank merge)
-  const int w = (int)std::min<int64_t>((int64_t)k + 1, g->n);
-  const int64_t PB = knnk::packed_part_bytes(m, w);
   const int ties = g->ctx[0]->tune_ties;
+  if ((rc = sharded_search(g, Q, m, k, metric, ties))) return rc;
+  if (ties && (rc = resolve_ties(g, m, k, metric))) return rc;
+  for (int i = 0; i < G; i++) {
+    HIP_G(hipSetDevice(g->devs[i]));
+    HIP_G(hipEventRecord(g->ev1[i], g->ctx[i]->stream));
+  }
   for (int i = 0; i < G; i++) {
     int64_t q0, mi;
     slice(i, q0, mi);
     HIP_G(hipSetDevice(g->devs[i]));
-    if ((rc = g->Q[i].ensure((size_t)m * d * sizeof(double)))) return rc;
-    // this GPU's lists packed [dist | idx | label] (one all-gather per step)
-    if ((rc = g->pk[i].ensure((size_t)PB))) return rc;
-    if (g->transport != XPORT_NONE && (rc = g->gk[i].ensure((size_t)G * PB))) return rc;
-    if ((rc = g->olab[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int32_t)))) return rc;
-    if ((rc = g->oflags[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int32_t)))) return rc;
-    if ((rc = g->oidx[i].ensure((size_t)std::max<int64_t>(mi, 1) * k * sizeof(int64_t)))) return rc;
-    if ((rc = g->odist[i].ensure((size_t)std::max<int64_t>(mi, 1) * k * sizeof(double)))) return rc;
-    if ((rc = g->tq[i].ensure((size_t)std::max<int64_t>(mi, 1) * sizeof(int)))) return rc;
-    if ((rc = g->tcnt[i].ensure(sizeof(int)))) return rc;
-    if (const int64_t sb = knnk::merge_scratch_bytes(G, w, k, mi))
-      if ((rc = g->ctx[i]->mrg.ensure((size_t)sb))) return rc;
+    if (mi > 0 && (rc = d2h(i, q0, mi))) return rc;
   }
-  // queries to the first GPU, broadcast to the rest
-  HIP_G(hipSetDevice(g->devs[0]));
-  HIP_G(hipMemcpyAsync(g->Q[0].p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice,
-                       g->ctx[0]->stream));
+  return finish();
+}
+
+int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
+                             int32_t nk, int32_t metric, int32_t* out_labels,
+                             const int32_t* truth, int64_t* out_correct) {
+  if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group classify sweep before set_train");
+  if (m < 0 || !out_labels || (m > 0 && !Q)) return knn_fail(KNN_ERR_ARG, "bad classify arguments");
+  if (m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be < 2^31 per call");
+  if (metric != KNN_METRIC_L2 && metric != KNN_METRIC_L1)
+    return knn_fail(KNN_ERR_ARG, "metric must be 0 (L2) or 1 (L1)");
+  int rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, g->n, &kmax))) return rc;
+  if ((truth != nullptr) != (out_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "truth and out_correct go together (both or neither)");
+  if (out_correct)
+    for (int j = 0; j < nk; j++) out_correct[j] = 0;
+  g->last_ties = 0;
+  if (m == 0) return KNN_OK;
+  const int G = g->ndev;
+  const int d = g->d;
+  auto slice = [&](int i, int64_t& q0, int64_t& mi) {
+    q0 = m * i / G;
+    mi = m * (i + 1) / G - q0;
+  };
+  if (g->mode == 1 && kmax == 0) {  // every K is 0 (cpp:324: max_label stays -1)
+    for (int64_t e = 0; e < (int64_t)nk * m; e++) out_labels[e] = -1;
+    return KNN_OK;
+  }
   for (int i = 0; i < G; i++) {
+    int64_t q0, mi;
+    slice(i, q0, mi);
     HIP_G(hipSetDevice(g->devs[i]));
-    HIP_G(hipEventRecord(g->ev0[i], g->ctx[i]->stream));
+    const size_t mi1 = (size_t)std::max<int64_t>(mi, 1);
+    if ((rc = g->slab[i].ensure(mi1 * nk * sizeof(int32_t)))) return rc;
+    if ((rc = g->struth[i].ensure(mi1 * sizeof(int32_t)))) return rc;
+    if ((rc = g->scorr[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
+    if (g->mode == 0 && (rc = g->Q[i].ensure(mi1 * d * sizeof(double)))) return rc;
   }
-  std::vector<void*> qb(G), sp(G), rp(G);
-  for (int i = 0; i < G; i++) {
-    qb[i] = g->Q[i].p;
-    sp[i] = g->pk[i].p;
-    rp[i] = g->gk[i].p;
+  // rank i's labels [nk][mi] -> columns [q0, q0 + mi) of the host's [nk][m];
+  // its correct counts are summed on the host once the devices are done
+  std::vector<std::vector<int64_t>> hc(G, std::vector<int64_t>(truth ? nk : 0, 0));
+  auto d2h = [&](int i, int64_t q0, int64_t mi) -> int {
+    hipStream_t s = g->ctx[i]->stream;
+    HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)m * sizeof(int32_t), g->slab[i].p,
+                           (size_t)mi * sizeof(int32_t), (size_t)mi * sizeof(int32_t), (size_t)nk,
+                           hipMemcpyDeviceToHost, s));
+    if (truth)
+      HIP_G(hipMemcpyAsync(hc[i].data(), g->scorr[i].p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    return KNN_OK;
+  };
+  auto finish = [&]() -> int {
+    double span = 0.0;
+    for (int i = 0; i < G; i++) {
+      HIP_G(hipSetDevice(g->devs[i]));
+      if (int e = sync_rank(g, i, "classify sweep")) return e;
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, g->ev0[i], g->ev1[i]) == hipSuccess)
+        span = std::max(span, (double)ms * 1e-3);
+    }
+    g->last_compute = span;
+    if (truth)
+      for (int i = 0; i < G; i++)
+        for (int j = 0; j < nk; j++) out_correct[j] += hc[i][j];
+    return KNN_OK;
+  };
+  if (g->mode == 0) {
+    for (int i = 0; i < G; i++) {
+      int64_t q0, mi;
+      slice(i, q0, mi);
+      HIP_G(hipSetDevice(g->devs[i]));
+      hipStream_t s = g->ctx[i]->stream;
+      if (mi <= 0) {
+        HIP_G(hipEventRecord(g->ev0[i], s));
+        HIP_G(hipEventRecord(g->ev1[i], s));
+        continue;
+      }
+      HIP_G(hipMemcpyAsync(g->Q[i].p, Q + q0 * d, (size_t)mi * d * sizeof(double),
+                           hipMemcpyHostToDevice, s));
+      if (truth)
+        HIP_G(hipMemcpyAsync(g->struth[i].p, truth + q0, (size_t)mi * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s));
+      HIP_G(hipEventRecord(g->ev0[i], s));
+      if ((rc = knn_classify_sweep_device(g->ctx[i], (const double*)g->Q[i].p, mi, ks, nk, metric,
+                                          (int32_t*)g->slab[i].p,
+                                          truth ? (const int32_t*)g->struth[i].p : nullptr,
+                                          truth ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
+                                          nullptr, nullptr, s)))
+        return rc;
+      HIP_G(hipEventRecord(g->ev1[i], s));
+    }
+    for (int i = 0; i < G; i++) {
+      int64_t q0, mi;
+      slice(i, q0, mi);
+      HIP_G(hipSetDevice(g->devs[i]));
+      if (mi > 0 && (rc = d2h(i, q0, mi))) return rc;
+    }
+    return finish();
   }
-  if ((rc = coll_bcast(g, qb, (size_t)m * d, ncclFloat64, 8, 0))) return rc;
+
+  // ---- train-sharded: partial lists and merges at kmax with the merges' tie
+  // queueing off; the sweep tie scan fills each rank's queue from its merged
+  // rows (every K of the list); the exchange restores the reference's order
+  // of the whole top kmax; the prefix votes read the all-rows labels
+  const int ties = g->ctx[0]->tune_ties;
+  if ((rc = sharded_search(g, Q, m, kmax, metric, 0))) return rc;
   for (int i = 0; i < G; i++) {
+    int64_t q0, mi;
+    slice(i, q0, mi);
+    if (mi <= 0 || !ties) continue;
     HIP_G(hipSetDevice(g->devs[i]));
-    unsigned char* pb = (unsigned char*)g->pk[i].p;
-    if ((rc = knn_search_partial_device(g->ctx[i], (const double*)g->Q[i].p, m, w, metric,
-                                        (double*)pb, (int64_t*)(pb + 8 * m * w),
-                                        (int32_t*)(pb + 16 * m * w), nullptr)))
-      return rc;
+    hipStream_t s = g->ctx[i]->stream;
+    if ((rc = g->sks[i].ensure((size_t)nk * sizeof(int32_t)))) return rc;
+    HIP_G(hipMemcpyAsync(g->sks[i].p, ks, (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    knnk::launch_sweep_tie_scan((const double*)g->odist[i].p, (const int64_t*)g->oidx[i].p,
+                                (const int32_t*)g->oflags[i].p, mi, kmax,
+                                (const int32_t*)g->labA[i].p, 0, (const int*)g->sks[i].p, nk, ties,
+                                (int*)g->tq[i].p, (int*)g->tcnt[i].p, g->ctx[i]->cu_count, s);
+    HIP_G(hipGetLastError());
   }
-  // one all-gather of the packed lists (≙ the reference's MPI_Gather, cpp:340)
-  if ((rc = coll_allgather(g, sp, rp, (size_t)PB))) return rc;
+  if (ties && (rc = resolve_ties(g, m, kmax, metric))) return rc;
   for (int i = 0; i < G; i++) {
     int64_t q0, mi;
     slice(i, q0, mi);
     HIP_G(hipSetDevice(g->devs[i]));
     hipStream_t s = g->ctx[i]->stream;
     if (mi > 0) {
-      const double* sk = (const double*)(g->transport != XPORT_NONE ? g->gk[i].p : g->pk[i].p);
-      knnk::MergeTies mt;
-      mt.mode = ties;
-      mt.q = (int*)g->tq[i].p;
-      mt.cnt = (int*)g->tcnt[i].p;
-      HIP_G(hipMemsetAsync(mt.cnt, 0, sizeof(int), s));
-      knnk::launch_merge_vote_partials(sk, nullptr, nullptr, G, m, w, k, (int32_t*)g->olab[i].p,
-                                       (int64_t*)g->oidx[i].p, (double*)g->odist[i].p,
-                                       (int32_t*)g->oflags[i].p, s, q0, mi, PB, g->ctx[i]->mrg.p,
-                                       mt);
-      HIP_G(hipGetLastError());
-    } else {
-      HIP_G(hipMemsetAsync(g->tcnt[i].p, 0, sizeof(int), s));
+      if (truth)
+        HIP_G(hipMemcpyAsync(g->struth[i].p, truth + q0, (size_t)mi * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s));
+      if ((rc = knn_vote_sweep_device(g->ctx[i], (const int64_t*)g->oidx[i].p, mi, kmax,
+                                      (const int32_t*)g->labA[i].p, 0, ks, nk,
+                                      (int32_t*)g->slab[i].p,
+                                      truth ? (const int32_t*)g->struth[i].p : nullptr,
+                                      truth ? (int64_t*)g->scorr[i].p : nullptr, s)))
+        return rc;
     }
-  }
-  if (ties && (rc = resolve_ties(g, m, k, metric))) return rc;
-  for (int i = 0; i < G; i++) {
-    HIP_G(hipSetDevice(g->devs[i]));
-    HIP_G(hipEventRecord(g->ev1[i], g->ctx[i]->stream));
+    HIP_G(hipEventRecord(g->ev1[i], s));
   }
   for (int i = 0; i < G; i++) {
     int64_t q0, mi;

@@ -35,6 +35,10 @@ struct Sink {
   int tie_mode;
   int* tie_q;
   int* tie_cnt;
+  // single: 1 = the search neither queues tied queries nor runs the
+  // reference-order pass (tie_mode 0 on the device): the K sweep queues them
+  // itself from the finished rows (launch_sweep_tie_scan) and runs the pass
+  int tie_defer = 0;
 };
 
 // Train-set side state resident in HBM.
@@ -348,6 +352,24 @@ int64_t tie_scratch_bytes(int64_t n, int class_cnt);
 void launch_tie_order(int metric, const TrainDev& t, const double* Q64, const int* tie_q,
                       const int* tie_cnt, int class_cnt, unsigned char* scratch, int64_t per_wg,
                       int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s);
+// K sweep (knn_sweep.hip): the reference's label at every K of a list from
+// one ordered top-kmax row per query (kmax >= every K).  ks: device array of
+// nk values in the caller's order (duplicates allowed); lab[idx - idx_base] is
+// the label of a row entry (idx -1: an empty slot; a row starting with one has
+// no neighbours and gets -1 at every K); cus sizes the grid.
+// tie scan: appends to tie_q (count in tie_cnt[0]) the queries whose label at
+// some K of the list the reference's order among equal distances could
+// change (mode as Sink::tie_mode); dist / idx [m][kmax] in (dist, idx) order,
+// flags [m] the search's flags for kmax (its KNN_FLAG_TIE_BOUNDARY bit).
+void launch_sweep_tie_scan(const double* dist, const int64_t* idx, const int32_t* flags, int64_t m,
+                           int kmax, const int32_t* lab, int64_t idx_base, const int* ks, int nk,
+                           int mode, int* tie_q, int* tie_cnt, int cus, hipStream_t s);
+// prefix votes: labels[j][q] (nk x m) = the vote over the first ks[j] entries
+// of row q; with truth [m], correct[j] += #{q : labels[j][q] == truth[q]}
+// (correct zeroed by the caller; one atomic per K per workgroup)
+void launch_sweep_vote(const int64_t* idx, int64_t m, int kmax, const int32_t* lab,
+                       int64_t idx_base, const int* ks, int nk, int32_t* labels,
+                       const int32_t* truth, unsigned long long* correct, int cus, hipStream_t s);
 // fp64 rows -> [hi(DP) | lo(DP)] bf16 rows of scale*x (candidate metric 2 = L2 via bf16x3)
 // rows of `out` are row_shorts 16-bit words; xl2/xl1 (train only, else null)
 // fill the padded row's seed floats after the 2*DP bf16 payload

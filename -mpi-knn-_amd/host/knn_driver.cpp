@@ -13,10 +13,17 @@
 // Extra flags: --gpus N (default 1), --mode query|train (multi-GPU layout),
 // --strict (exit 1 unless N_* divisible by --gpus, as MPI_Abort cpp:127-129),
 // --threads T (CSV parsing threads), --output path, --timings (per-phase
-// seconds on stderr; stdout stays the reference's).
+// seconds on stderr; stdout stays the reference's),
+// --K_list k1,k2,... (needs --Validation true): the validation pass scores
+// every K of the list from one search (knn_group_classify_sweep), prints
+// "K = <k> accuracy = <acc>" per K in list order, selects the first K whose
+// accuracy strictly exceeds the running best (the reference's first-to-exceed
+// idiom, cpp:332-335), prints "selected K = <k>" and the reference's
+// "accuracy = <acc>" line for it, and runs the test pass at that K.
 // The timed region spans the same work as the reference (barrier to
 // barrier: CSV parsing, distribution, normalisation, both passes, output).
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +53,7 @@ struct Config {
   bool strict = false;
   int threads = 0;
   bool timings = false;
+  std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
 };
 
 bool parse_bool(const std::string& v) { return v == "true" || v == "1" || v == "yes"; }
@@ -56,7 +64,27 @@ void usage() {
           "  [--class_cnt C] [--Euclidean_distance true|false] [--Normalize true|false]\n"
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
-          "  [--threads T] [--timings]\n");
+          "  [--threads T] [--timings] [--K_list K1,K2,...]\n"
+          "  --K_list needs --Validation true: one search scores every K on the validation\n"
+          "  set; the test pass runs at the first K with the best accuracy\n");
+}
+
+// "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit
+bool parse_k_list(const std::string& v, std::vector<int32_t>& out) {
+  out.clear();
+  size_t i = 0;
+  while (true) {
+    long long k = 0;
+    size_t digits = 0;
+    for (; i < v.size() && v[i] >= '0' && v[i] <= '9'; ++i, ++digits) {
+      k = k * 10 + (v[i] - '0');
+      if (k > INT32_MAX) return false;
+    }
+    if (!digits) return false;
+    out.push_back((int32_t)k);
+    if (i == v.size()) return true;
+    if (v[i++] != ',') return false;
+  }
 }
 
 int parse_args(int argc, char** argv, Config& c) {
@@ -89,6 +117,12 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "mode") c.mode = (v == "train" || v == "1") ? 1 : 0;
     else if (a == "strict") c.strict = parse_bool(v);
     else if (a == "threads") c.threads = atoi(v.c_str());
+    else if (a == "K_list") {
+      if (!parse_k_list(v, c.K_list)) {
+        fprintf(stderr, "--K_list takes a comma-separated list of non-negative integers\n");
+        return 1;
+      }
+    }
     else { fprintf(stderr, "unknown flag --%s\n", a.c_str()); usage(); return 1; }
   }
   return 0;
@@ -123,6 +157,14 @@ int main(int argc, char** argv) {
     die("bad configuration");
   if (c.strict && (c.N_train % c.gpus || c.N_test % c.gpus || (c.Validation && c.N_val % c.gpus)))
     die("N_train/N_test/N_val not divisible by the number of GPUs (--strict, cpp:127-129)");
+  if (!c.K_list.empty()) {
+    if (!c.Validation) die("--K_list needs --Validation true (K is judged on the validation set)");
+    if (c.N_val <= 0) die("--K_list needs a validation set (N_val > 0)");
+    if (c.K_list.size() > 4096) die("--K_list takes at most 4096 values");
+    for (size_t i = 0; i < c.K_list.size(); i++)
+      if (c.K_list[i] > c.N_train)
+        die("--K_list entry " + std::to_string(c.K_list[i]) + " exceeds N_train");
+  }
 
   knn_group* g = nullptr;
   if (knn_group_create(&g, c.gpus, nullptr, c.mode)) die(knn_last_error());
@@ -159,7 +201,28 @@ int main(int argc, char** argv) {
   phase("set_train");
   const int metric = c.Euclidean_distance ? KNN_METRIC_L2 : KNN_METRIC_L1;
 
-  if (c.Validation) {  // cpp:308-349
+  if (!c.K_list.empty()) {  // the validation pass (cpp:308-349) for every K of the list
+    const int32_t nk = (int32_t)c.K_list.size();
+    std::vector<int32_t> pred((size_t)nk * c.N_val);
+    std::vector<int64_t> correct(nk, 0);
+    if (knn_group_classify_sweep(g, Xva.data(), c.N_val, c.K_list.data(), nk, metric, pred.data(),
+                                 Lva.data(), correct.data()))
+      die(knn_last_error());
+    double best = -1.0, best_acc = 0.0;
+    for (int32_t i = 0; i < nk; i++) {
+      double acc = (double)correct[i];  // acc_calc, cpp:69-84
+      acc /= c.N_val;
+      std::cout << "K = " << c.K_list[i] << " accuracy = " << acc << std::endl;
+      if (acc > best) {  // first to strictly exceed, like cpp:332-335
+        best = acc;
+        best_acc = acc;
+        c.K = c.K_list[i];
+      }
+    }
+    std::cout << "selected K = " << c.K << std::endl;
+    std::cout << "accuracy = " << best_acc << std::endl;
+    phase("validation");
+  } else if (c.Validation) {  // cpp:308-349
     std::vector<int32_t> pred(c.N_val);
     if (c.N_val > 0 &&
         knn_group_classify(g, Xva.data(), c.N_val, c.K, metric, pred.data(), nullptr, nullptr, nullptr))

@@ -39,6 +39,8 @@ EXPORTED = (
     "knn_timing_totals", "knn_rescan_totals", "knn_last_kernel_name", "knn_tie_totals",
     "knn_shard_distances_device", "knn_tie_resolve_device", "knn_group_transport",
     "knn_group_last_tie_count", "knn_group_set_precision", "knn_group_set_tuning",
+    "knn_vote_sweep_device", "knn_classify_sweep_device", "knn_classify_sweep",
+    "knn_group_classify_sweep",
 )
 GROUP_RCCL = 0x100  # knn_group_create mode flag: RCCL collectives also at one GPU
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1, 2
@@ -133,6 +135,11 @@ def lib():
         "knn_group_last_tie_count": ([P], i64),
         "knn_group_set_precision": ([P, ctypes.c_int], ctypes.c_int),
         "knn_group_set_tuning": ([P, ctypes.c_char_p, i64], ctypes.c_int),
+        "knn_vote_sweep_device": ([P, P, i64, i32, P, i64, P, i32, P, P, P, P], ctypes.c_int),
+        "knn_classify_sweep_device": ([P, P, i64, P, i32, i32, P, P, P, P, P, P, P],
+                                      ctypes.c_int),
+        "knn_classify_sweep": ([P, P, i64, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
+        "knn_group_classify_sweep": ([P, P, i64, P, i32, i32, P, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -225,6 +232,51 @@ class Classifier:
         if return_neighbors:
             return labels, idx[:, :k], dist[:, :k], flags
         return labels
+
+    def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False):
+        """Labels for every K of `ks` (any order, duplicates allowed) from one
+        search at max(ks): labels int32[nk, m], row i for ks[i].  With `truth`
+        (int32[m]) also correct int64[nk] = (labels[i] == truth).sum().  With
+        return_neighbors also (idx[m, kmax], dist[m, kmax], flags[m])."""
+        Q = _f64(Q)
+        m = Q.shape[0]
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk = ks.shape[0]
+        kmax = int(ks.max()) if nk else 0
+        labels = np.empty((nk, m), np.int32)
+        flags = np.empty(m, np.int32)
+        idx = np.empty((m, max(kmax, 1)), np.int64) if return_neighbors else None
+        dist = np.empty((m, max(kmax, 1)), np.float64) if return_neighbors else None
+        if truth is not None:
+            truth = np.ascontiguousarray(truth, dtype=np.int32)
+            if truth.shape != (m,):
+                raise ValueError("truth must have one label per query")
+        correct = np.zeros(nk, np.int64) if truth is not None else None
+        _check(lib().knn_classify_sweep(self._h, _ptr(Q), m, _ptr(ks), nk, int(metric),
+                                        _ptr(labels), _ptr(truth), _ptr(correct), _ptr(idx),
+                                        _ptr(dist), _ptr(flags)))
+        out = (labels,) if truth is None else (labels, correct)
+        if return_neighbors:
+            out += (idx[:, :kmax], dist[:, :kmax], flags)
+        return out[0] if len(out) == 1 else out
+
+    def classify_sweep_device(self, dQ_ptr, m, ks, metric, d_labels, d_truth=None,
+                              d_correct=None, d_idx=None, d_dist=None, d_flags=None, stream=None):
+        """Device-pointer sweep (enqueue only); ks is a host sequence."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_classify_sweep_device(self._h, dQ_ptr, m, _ptr(ks), ks.shape[0],
+                                               int(metric), d_labels, d_truth, d_correct, d_idx,
+                                               d_dist, d_flags, stream))
+
+    def vote_sweep_device(self, d_idx, m, kmax, d_lab, ks, d_labels, idx_base=0, d_truth=None,
+                          d_correct=None, stream=None):
+        """Prefix votes of ordered neighbour rows d_idx [m][kmax] (device
+        pointers; label of an entry = d_lab[idx - idx_base]) at every K of the
+        host sequence ks: d_labels [nk][m], d_correct [nk] with d_truth."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_vote_sweep_device(self._h, d_idx, m, int(kmax), d_lab, int(idx_base),
+                                           _ptr(ks), ks.shape[0], d_labels, d_truth, d_correct,
+                                           stream))
 
     def classify_device(self, dQ_ptr, m, k, metric, d_labels, d_idx=None, d_dist=None,
                         d_flags=None, stream=None):
@@ -399,6 +451,23 @@ class Group:
             return labels, idx[:, :k], dist[:, :k], flags
         return labels
 
+    def classify_sweep(self, Q, ks, metric=L2, truth=None):
+        """Classifier.classify_sweep over the group: labels int32[nk, m], and
+        with `truth` also correct int64[nk] (summed over the ranks)."""
+        Q = _f64(Q)
+        m = Q.shape[0]
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk = ks.shape[0]
+        labels = np.empty((nk, m), np.int32)
+        if truth is not None:
+            truth = np.ascontiguousarray(truth, dtype=np.int32)
+            if truth.shape != (m,):
+                raise ValueError("truth must have one label per query")
+        correct = np.zeros(nk, np.int64) if truth is not None else None
+        _check(lib().knn_group_classify_sweep(self._h, _ptr(Q), m, _ptr(ks), nk, int(metric),
+                                              _ptr(labels), _ptr(truth), _ptr(correct)))
+        return labels if truth is None else (labels, correct)
+
     def last_compute_seconds(self):
         return float(lib().knn_group_last_compute_seconds(self._h))
 
@@ -411,7 +480,11 @@ class Group:
 
 def run_driver(cfg: KnnConfig, workdir, gpus=1, mode="query", extra=()):
     """Runs the native drop-in driver (bin/knn_mpi_amd) the way `mpiexec
-    knn_mpi` runs the reference, in `workdir`; returns its stdout."""
+    knn_mpi` runs the reference, in `workdir`; returns its stdout.
+    `extra` takes further driver flags, e.g. ["--K_list", "1,3,5"] (needs
+    Validation: one search scores every K on the validation set, prints
+    "K = <k> accuracy = <acc>" per K and "selected K = <k>", and the test
+    pass runs at the selected K)."""
     if not os.path.exists(DRIVER_PATH):
         raise KnnError("driver not built: " + DRIVER_PATH)
     args = [DRIVER_PATH]

@@ -136,6 +136,51 @@ int knn_classify_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t k, in
                         int32_t* d_labels, int64_t* d_idx, double* d_dist, int32_t* d_flags,
                         void* stream);
 
+/* ---- K sweep: labels (and accuracy counts) for a list of K from ONE search.
+ * The reference judges K by its validation pass (cpp:308-343), one run per
+ * compiled-in K.  Its neighbour order does not depend on K (std::sort over
+ * all N_train records, cpp:323; the vote scans the first K, cpp:324-337), so
+ * the label at every K <= kmax is a prefix vote over one ordered top-kmax
+ * row: these calls search once at kmax = max(ks) and vote every prefix.
+ * ks: host array of nk values in any order, duplicates allowed, 1 <= nk <=
+ * 4096, 0 <= ks[i] <= n_train (KNN_ERR_ARG names the offending entry).
+ * Labels are laid out [nk][m]: row i belongs to ks[i] and equals what
+ * knn_classify returns for k = ks[i] (K = 0: -1; a non-finite query: -1 at
+ * every K).  truth [m] (nullable) are the queries' true labels: correct[i]
+ * (int64, [nk]) then receives #{q : labels[i][q] == truth[q]} (≙ cnt of
+ * cpp:341-343 per K); truth and correct go together (KNN_ERR_ARG otherwise).
+ * Ties: with "ties" = 1 the queries whose label AT ANY K of the list the
+ * reference's order among equal distances could change are re-ordered as its
+ * std::sort orders them (KNN_FLAG_TIE_REF; "ties" = 2: every query with equal
+ * distances in its top kmax; 0: none).
+ *
+ * knn_vote_sweep_device: the prefix votes alone, over caller-supplied ordered
+ * neighbour rows d_idx [m][kmax] (global indices; -1 = empty slot, a row
+ * starting with -1 gets -1 at every K) with label d_lab[idx - idx_base]
+ * (building block; also for callers that merged lists themselves).  Here
+ * ks[i] <= kmax.  Device pointers except ks; enqueue only. */
+int knn_vote_sweep_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_t kmax,
+                          const int32_t* d_lab, int64_t idx_base, const int32_t* ks, int32_t nk,
+                          int32_t* d_labels, const int32_t* d_truth, int64_t* d_correct,
+                          void* stream);
+/* Search at kmax = max(ks), sweep tie scan, reference-order pass, prefix
+ * votes: enqueued on `stream` like knn_classify_device (no host wait).
+ * d_labels [nk*m] required; d_truth / d_correct as above; d_idx / d_dist
+ * [m*kmax] and d_flags [m] nullable (internal rows are used when null): the
+ * top kmax of each query and the tie bits for kmax, KNN_FLAG_TIE_REF on the
+ * rows the sweep re-ordered.  KNN_ERR_STATE before set_train. */
+int knn_classify_sweep_device(knn_ctx* ctx, const double* dQ, int64_t m, const int32_t* ks,
+                              int32_t nk, int32_t metric, int32_t* d_labels,
+                              const int32_t* d_truth, int64_t* d_correct, int64_t* d_idx,
+                              double* d_dist, int32_t* d_flags, void* stream);
+/* Host-pointer twin (waits for the result): out_labels [nk*m], out_correct
+ * [nk] (required iff truth), out_idx / out_dist [m*kmax], out_flags [m]
+ * nullable. */
+int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks, int32_t nk,
+                       int32_t metric, int32_t* out_labels, const int32_t* truth,
+                       int64_t* out_correct, int64_t* out_idx, double* out_dist,
+                       int32_t* out_flags);
+
 /* Train-sharded building block: exact top-w of THIS context's shard for
  * each query, sorted by (dist, global idx), with each neighbour's label.
  * Rows beyond the shard size are padded with dist=+inf, idx=-1, label=-1.
@@ -349,6 +394,16 @@ int knn_group_set_train(knn_group* g, const double* X, const int32_t* labels, in
 int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int32_t metric,
                        int32_t* out_labels, int64_t* out_idx, double* out_dist,
                        int32_t* out_flags);
+/* K sweep over the group (see knn_classify_sweep): out_labels [nk*m] in host
+ * query order, out_correct [nk] summed over the ranks (required iff truth).
+ * mode 0: each rank sweeps its query slice.  mode 1: the partial lists and
+ * the merge run at kmax, the sweep tie scan fills each rank's tie queue, the
+ * cross-shard exchange restores the reference's order, and the prefix votes
+ * read the all-rows label array; knn_group_last_tie_count reports the queries
+ * the exchange resolved. */
+int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
+                             int32_t nk, int32_t metric, int32_t* out_labels,
+                             const int32_t* truth, int64_t* out_correct);
 /* Seconds of the last group classify spent between the first enqueue and
  * the last device completion (device-resident inputs, excludes H2D/D2H). */
 double knn_group_last_compute_seconds(knn_group* g);
