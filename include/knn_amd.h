@@ -105,7 +105,11 @@ int knn_destroy(knn_ctx* ctx);
 /* Train set from host memory: X row-major n x d fp64 (Data_train, cpp:140),
  * labels (Train_label, cpp:141) with 0 <= label < class_cnt.  The library
  * copies both to HBM (≙ MPI_Bcast cpp:224-225).  KNN_ERR_ARG for a label out
- * of range or a non-finite value (NaN / inf) anywhere in X. */
+ * of range or a non-finite value (NaN / inf) anywhere in X, and for a train
+ * set with |x - mean| >= 2^400 in any dimension (mean: the dimension's mean
+ * over the train rows; beyond that the candidate passes' operands could
+ * overflow).  A refused train set leaves the context without one: classify
+ * returns KNN_ERR_STATE until a set_train succeeds. */
 int knn_set_train(knn_ctx* ctx, const double* X, const int32_t* labels, int64_t n,
                   int32_t d, int32_t class_cnt);
 /* Same from device memory on ctx's GPU (e.g. after an RCCL broadcast).
