@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "knn_kernels.h"
+#include "knn_plan.h"
 
 struct DevBuf {
   void* p = nullptr;
@@ -55,39 +56,12 @@ struct knn_ctx {
   hipEvent_t done_ev = nullptr;
   bool auto_pending = false;
   int64_t auto_m = 0;
-  int tune_R = 0, tune_S = 0;  // 0 = automatic
-  int tune_ablate = 0;         // timing-only kernel ablations
-  int tune_nw = 0;             // resident kernel waves per workgroup (0 = auto)
-  int tune_s3q = -1;           // fp16 S3 on the 16x16x32 layout: -1 auto, 0 off, 1 on
-  int tune_qres = -1;          // query-resident fp16 kernel for d > 256 (knn_cand_qres.hip): -1 auto, 0 off
-  int tune_gk = -1;            // what the lists publish into gthr (-1 auto, 0 list R-th, 1..16)
-  int tune_xhswz = 1;          // fp16 train image chunk swizzle (xh_swz): 1 on, 0 off (A/B)
-  int tune_fp16 = -1;          // fp16 candidate pass: -1 auto, 0 off, 1 on
-  int tune_i8 = -1;            // int8 candidate pass: -1 auto, 0 off, 1 on (where the data allow)
-  int tune_i8w = -1;           // int8 on 32x32x32 (metric 6): -1 auto (where it pads less), 0 off, 1 on
-  int tune_ties = 1;           // reference tie order: 0 off, 1 vote-affecting ties, 2 all ties
-  int tune_m16 = -1;           // bf16x3 on the 16x16x32 MFMA layout: -1 auto, 0 off, 1 on
-  int64_t tune_seed = 0;       // seeded thresholds: 0 / -1 off, N sample rows (experiment)
-  // region order (knn_order.hip): -1 auto, 0 off, 1 on, N >= 2 that many
-  // regions.  The train layout is decided at set_train; a train set laid out
-  // by region still serves calls with 0 (queries in call order, streams
-  // starting at each split's first tile).
-  int tune_order = -1;
-  int ord_P = 0;               // regions of the current train layout (0: train order)
-  // norm blocks (knn_order.hip): -1 auto (integer-coded train sets, d <= 256),
-  // 0 off, 1 on; ord_nb: the current layout has them (ord_perm / ord_ipos valid)
-  int tune_nblk = -1;
-  int tune_gg = -1;            // gthr slot groups of the resident kernel: -1 auto, 4 or 8
-  int tune_i8resc = -1;        // int8 rescan filter (metric 6): -1 auto (on), 0 off
-  int tune_qblk = 0;           // resident kernel workgroup order: 0 split-major, B query blocks
-  bool ord_nb = false;
+  knnk::Tuning tune;     // knn_set_tuning (knn_plan.h)
+  int ord_P = 0;         // regions of the current train layout (0: train order)
+  bool ord_nb = false;   // the current layout has norm blocks (ord_perm / ord_ipos valid)
   // ints of ord_bcnt known to be zero (the int8 query builder clears the
   // region sort's block counts after the sort read them; 0: unknown)
   int64_t ord_bcnt_zero = 0;
-  int tune_s3gq = 0;           // S3 kernel: largest XCD query-tile grouping (0 = kS3GqMax)
-  // query streams start at one of N phases of the region chain (P regions in
-  // N groups; -1 auto = 8, 0 = at the query tile's own region)
-  int tune_ophase = -1;
   // sample image of the seeding pre-pass (strided train rows in the image
   // format of kernel metric smp_kind at width smp_dp; 0 = not built)
   int smp_kind = 0, smp_dp = 0, smp_swz = -1;

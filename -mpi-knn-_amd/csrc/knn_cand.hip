@@ -559,52 +559,6 @@ cand_s3_kernel(const unsigned short* XT, const float* XS, const unsigned short* 
 }
 
 
-int pad_dim(int d) {
-#define KNN_CASE(v) if (d <= v) return v;
-  KNN_DP_LIST(KNN_CASE)
-#undef KNN_CASE
-  return (d + kStreamDC - 1) / kStreamDC * kStreamDC;  // streamed kernel
-}
-
-bool cand_supported(int DP) { return DP > 0 && pad_dim(DP) == DP; }
-
-// bf16x3 path: resident kernel for DP <= 256 (a multiple of 16 in the
-// resident list), the S3 stream kernel above it (any multiple of 16).
-int pad_dim_bf16x3(int d) {
-  const int d16 = (d + 15) / 16 * 16;
-  if (d16 > 256) return d16;
-  const int DP = pad_dim(d16);
-  return (DP <= 256 && DP % 16 == 0) ? DP : -1;
-}
-
-bool bf16x3_streamed(int DP) { return DP > 256; }
-
-// fp16 path: resident 16x16x32 kernel, DP % 32 == 0 and <= 256.
-int pad_dim_fp16(int d) {
-  const int DP = pad_dim((d + 31) / 32 * 32);
-  return (DP <= 256 && DP % 32 == 0) ? DP : -1;
-}
-
-// int8 path: the resident 16x16x64 kernel, DP a multiple of 64, <= 256
-int pad_dim_i8(int d) {
-  const int DP = (d + 63) / 64 * 64;
-  return DP <= 256 ? DP : -1;
-}
-
-// int8 on the 32x32x32 kernel (metric 6): the smallest resident DP >= d
-// that is a multiple of 32 (d = 96 -> 96, where 16x16x64 pads to 128)
-int pad_dim_i8w(int d) {
-  for (int DP : {32, 64, 96, 128, 160, 192, 256})
-    if (DP >= d) return DP;
-  return -1;
-}
-
-// fp16 S3 kernel above 256 dims: any multiple of 32
-int pad_dim_fp16_s3(int d) {
-  const int DP = (d + 31) / 32 * 32;
-  return DP > 256 ? DP : -1;
-}
-
 int s3_blocks_per_cu(int R) {
   return R == 8 ? occupancy_of(cand_s3_kernel<8, false, false>, 512)
                 : occupancy_of(cand_s3_kernel<16, false, false>, 512);
@@ -613,15 +567,6 @@ int s3_blocks_per_cu(int R) {
 int s3h_blocks_per_cu(int R) {
   return R == 8 ? occupancy_of(cand_s3_kernel<8, true, false>, 512)
                 : occupancy_of(cand_s3_kernel<16, true, false>, 512);
-}
-
-// the S3 grouping (s3_map) that n_qt and S admit, the largest up to gq_max
-// (a row chunk then serves gq workgroups of the XCD, a query chunk 32 / gq):
-// 32, 16, 8, 4, 2, 1, else 0
-int s3_group(int n_qt, int S, int gq_max) {
-  for (int gq : {32, 16, 8, 4, 2, 1})
-    if (gq <= gq_max && n_qt % gq == 0 && S % (32 / gq) == 0) return gq;
-  return 0;
 }
 
 void launch_cand_s3(const unsigned short* XT, const float* XS, const unsigned short* QT, int DP,

@@ -868,6 +868,4 @@ static int occupancy_of(KernelT k, int threads) {
   return cache[key] = nb > 0 ? nb : 1;
 }
 
-#define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
-
 }  // namespace knnk

@@ -1,0 +1,32 @@
+// knn_dims.h -- the dimensions and padding rules that the kernels and the
+// host-only search plan (knn_plan.h) share.  Plain C++: no HIP types, so the
+// plan and its checker compile without a device toolchain.
+#pragma once
+#include <stdint.h>
+
+namespace knnk {
+
+constexpr int kQPB = 128;        // queries per candidate workgroup (4 waves x 32)
+constexpr int kMaxUnion = 1024;  // max candidates kept per query across all lists
+constexpr int kStreamDC = 32;    // dims per LDS chunk in the large-d kernel
+constexpr int kS3Rows = 256;        // S3 kernel: train rows per tile = queries per workgroup
+constexpr int kS3GqMax = 4;         // S3: default largest XCD grouping of query tiles (s3_group)
+constexpr int kGthrSlots = 8;                // slots per query in gthr
+constexpr int kRescanFastQueries = 65536;  // failed queries per call the fast path serves
+constexpr int kRegionMax = 64;  // regions (k-means centroids) at most
+constexpr int kNormWin = 16384;
+
+int pad_dim(int d);                 // padded dim the candidate kernels run at
+int pad_dim_bf16x3(int d);          // padded dim of the bf16x3 kernel, -1 if unsupported
+int pad_dim_fp16(int d);            // padded dim of the fp16 kernel (metric 4), -1 if unsupported
+bool bf16x3_streamed(int DP);       // bf16x3 at this DP runs the S3 stream kernel
+// S3 workgroup grouping for n_qt query tiles and S splits (knn_cand.hip, s3_map)
+int s3_group(int n_qt, int S, int gq_max = kS3GqMax);
+int pad_dim_fp16_s3(int d);         // padded dim of the fp16 S3 image (multiple of 32, > 256)
+bool cand_supported(int DP);
+int pad_dim_i8(int d);  // padded dim of the int8 kernel (a multiple of 64, <= 256), -1 if none
+int pad_dim_i8w(int d); // padded dim of the int8 32x32x32 kernel (metric 6), -1 if none
+
+#define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
+
+}  // namespace knnk

@@ -760,7 +760,7 @@ int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int3
       for (int64_t q = 0; q < m; q++) out_flags[q] = 0;
     return KNN_OK;
   }
-  const int ties = g->ctx[0]->tune_ties;
+  const int ties = g->ctx[0]->tune.ties;
   if ((rc = sharded_search(g, Q, m, k, metric, ties))) return rc;
   if (ties && (rc = resolve_ties(g, m, k, metric))) return rc;
   for (int i = 0; i < G; i++) {
@@ -879,7 +879,7 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
   // queueing off; the sweep tie scan fills each rank's queue from its merged
   // rows (every K of the list); the exchange restores the reference's order
   // of the whole top kmax; the prefix votes read the all-rows labels
-  const int ties = g->ctx[0]->tune_ties;
+  const int ties = g->ctx[0]->tune.ties;
   if ((rc = sharded_search(g, Q, m, kmax, metric, 0))) return rc;
   for (int i = 0; i < G; i++) {
     int64_t q0, mi;

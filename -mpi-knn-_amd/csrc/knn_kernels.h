@@ -4,15 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_dims.h"
+
 namespace knnk {
 
-constexpr int kQPB = 128;        // queries per candidate workgroup (4 waves x 32)
 constexpr int kTR = 32;          // train rows per MFMA sub-tile of the resident kernel
 constexpr int kResTileRows = 64; // resident kernel: train rows per staged tile (2 sub-tiles)
-constexpr int kMaxUnion = 1024;  // max candidates kept per query across all lists
 constexpr int kSortN = 2048;     // rows per exact-rescan chunk / reduce block
 constexpr int kMaxK = 1000;      // largest k served (k+1 <= kMaxUnion)
-constexpr int kStreamDC = 32;    // dims per LDS chunk in the large-d kernel
 constexpr int kRowAlign = 256;   // train rows are padded to a multiple of this (<= one staged tile)
 
 enum { MODE_SINGLE = 0, MODE_PARTIAL = 1 };
@@ -62,12 +61,6 @@ struct TrainDev {
   const int* ipos = nullptr;  // [n]
 };
 
-int pad_dim(int d);                 // padded dim the candidate kernels run at
-int pad_dim_bf16x3(int d);          // padded dim of the bf16x3 kernel, -1 if unsupported
-int pad_dim_fp16(int d);            // padded dim of the fp16 kernel (metric 4), -1 if unsupported
-bool bf16x3_streamed(int DP);       // bf16x3 at this DP runs the S3 stream kernel
-constexpr int kS3Rows = 256;        // S3 kernel: train rows per tile = queries per workgroup
-constexpr int kS3GqMax = 4;         // S3: default largest XCD grouping of query tiles (s3_group)
 int s3_blocks_per_cu(int R);
 // S3 kernel (bf16x3, DP > 256): XT/QT are tile-chunk images made by
 // launch_prep_split_tiled, XS the per-row seeds [n_pad]; n_pad and m_pad are
@@ -97,9 +90,6 @@ bool qres_supported(int DP);
 bool launch_cand_qres(const unsigned short* XT, const float* XS, const unsigned short* QT, int DP,
                       int64_t n_pad, int S, int n_qt, float* out_v, int* out_i, uint32_t* gthr, int gk,
                       hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
-// S3 workgroup grouping for n_qt query tiles and S splits (knn_cand.hip, s3_map)
-int s3_group(int n_qt, int S, int gq_max = kS3GqMax);
-int pad_dim_fp16_s3(int d);         // padded dim of the fp16 S3 image (multiple of 32, > 256)
 // fp64 rows -> fp16 S3 tile-chunk images of mult * 2^jx (x - mu) (knn_prep.hip);
 // train: seed_out[row] = seed_src[row] (+inf on pad rows) and the running max
 // of the rows' squared representation error in dx2max; queries: seed_out =
@@ -108,7 +98,6 @@ void launch_prep_half_tiled(const double* X64, const double* mu, int64_t n, int 
                             int64_t n_pad, int jx, double mult, unsigned short* out,
                             const float* seed_src, float* seed_out, const float* valid,
                             unsigned long long* dx2max, hipStream_t s, const int* perm = nullptr);
-bool cand_supported(int DP);
 // train rows per tile of the candidate kernel serving (kernel metric, DP):
 // split s of a launch walks tiles s, s + S, ... (rows (r / tile) % S == s)
 int cand_tile_rows(int metric, int DP);
@@ -148,7 +137,6 @@ struct CandLaunch {
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 constexpr uint32_t kGthrInit = 0xFF800000u;  // order-preserving key of +inf
-constexpr int kGthrSlots = 8;                // slots per query in gthr
 // gthr init: slots [0, active) = +inf keys, the rest 0 (never the max)
 void launch_fill_gthr(uint32_t* g, int64_t m_pad, int active, hipStream_t s);
 // seeded thresholds: the need-th smallest of each query's U pre-pass list entries
@@ -239,7 +227,6 @@ void launch_merge_rerank(int metric, const float* cv, const int* ci, int NL, int
                          const RescanPrep& rp, hipStream_t s);
 constexpr int kRescanCap = 1024;        // rows a fast rescan may append per query
 constexpr int kRescanStageMaxDP = 256;  // fast rescan stages rows in LDS up to this DP
-constexpr int kRescanFastQueries = 65536;  // failed queries per call the fast path serves
 // Device-driven rescan (knn_select.hip): every buffer sized for `cap` fast-
 // path queries (cap <= m); the merge fills q/tau and counts cnt[0].
 struct RescanBufs {
@@ -340,8 +327,6 @@ void launch_prep_i8_queries(const double* Q64, const double* mu, double scale, i
                             int64_t m_pad, int s, signed char* out, float* valid, hipStream_t st,
                             const int* qperm, uint32_t* gthr, int active, int* zero = nullptr,
                             int64_t nzero = 0, int* zero4 = nullptr);
-int pad_dim_i8(int d);  // padded dim of the int8 kernel (a multiple of 64, <= 256), -1 if none
-int pad_dim_i8w(int d); // padded dim of the int8 32x32x32 kernel (metric 6), -1 if none
 // The reference's exact neighbour order on exact distance ties (knn_select.hip,
 // "reference tie order"): libstdc++ std::sort (introsort) emulated over all
 // n exact distances of each listed query, restricted to the ranges that
@@ -394,7 +379,6 @@ void launch_prep_split(const double* X64, const double* mu, int64_t n, int d, in
                        const float* xl2, const float* xl1, hipStream_t s, const int* perm = nullptr);
 
 // Region order (knn_order.hip).  Features are the fp32 operands 2^jx (x - mu).
-constexpr int kRegionMax = 64;  // regions (k-means centroids) at most
 // out[r] = rank[nearest centroid of row r * stride] (rank null: the centroid)
 // Assignment on bf16 MFMA against a centroid image (launch_region_kmeans):
 // out[r] = rank[nearest centroid of row r * stride] (rank null: the centroid);
@@ -434,7 +418,6 @@ void launch_region_sort_queries(const double* Q, const double* mu, int64_t m, in
 // key holds n uint32 of scratch.  perm0 must not alias perm / ipos.  il: the
 // int8 kernel metric (5 / 6) whose lane lists the norm ranks of each 32-row
 // sub-tile are interleaved over (0: sorted order).
-constexpr int kNormWin = 16384;
 void launch_norm_blocks(const double* X, const double* cent, int s, const double* mu, int64_t n,
                         int d, const int* perm0, uint32_t* key, int* perm, int* ipos, int il,
                         hipStream_t st);
