@@ -607,11 +607,12 @@ static int tie_setup(knn_ctx* ctx, int64_t m, Sink& sink, TieScratch& ts, bool z
   return KNN_OK;
 }
 // queries with exact distance ties: the reference's std::sort order
+// excl (nullable): per-query excluded train rows (K sweep under exclusion)
 static void tie_order(knn_ctx* ctx, const TieScratch& ts, int metric, const double* dQ,
-                      const Sink& sink, hipStream_t s) {
+                      const Sink& sink, hipStream_t s, const int64_t* excl = nullptr) {
   launch_tie_order(metric, ctx->train, dQ, sink.tie_q, sink.tie_cnt, ctx->class_cnt,
                    (unsigned char*)ctx->tie_ws.p, ts.per, ts.nwg, sink,
-                   (unsigned long long*)ctx->totals.p + 2, s);
+                   (unsigned long long*)ctx->totals.p + 2, s, excl);
 }
 
 static const KernelFacts kFacts = {cand_blocks_per_cu, s3q_blocks_per_cu, cand_queries_per_wave,
@@ -1170,6 +1171,154 @@ int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* 
     HIP_TRY(hipMemcpyAsync(out_dist, ctx->o_dist.p, (size_t)m * kmax * sizeof(double),
                            hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return KNN_OK;
+}
+
+// ---- K sweep under exclusion / leave-one-out (knn_loo.hip, cpp:308-343 with
+// the train set as its own validation set)
+
+int knn_classify_sweep_excl_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                   const int64_t* d_excl, const int32_t* ks, int32_t nk,
+                                   int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                   int64_t* d_correct, int64_t* d_idx, double* d_dist,
+                                   int32_t* d_flags, void* stream) {
+  if (!d_excl)  // nothing excluded for any query: the plain sweep
+    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
+                                     d_idx, d_dist, d_flags, stream);
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  const TrainDev& t = ctx->train;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, t.n - 1, &kmax))) return rc;  // one row may be taken out
+  if (kmax == 0)  // every K is 0: no neighbour is read
+    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
+                                     d_idx, d_dist, d_flags, stream);
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const int* dks = (const int*)ctx->sw_ks.p;
+  // one search at kmax + 1 into internal rows (neither queues ties nor runs
+  // the reference-order pass), compacted into the caller's kmax-entry rows
+  const int k1 = kmax + 1;
+  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->loo_idx.ensure((size_t)m * k1 * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->loo_dist.ensure((size_t)m * k1 * sizeof(double)))) return rc;
+  if ((rc = ctx->loo_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
+  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
+  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  Sink sink{};
+  sink.mode = MODE_SINGLE;
+  sink.k = k1;
+  sink.idx_off = ctx->idx_off;
+  sink.labels = (int32_t*)ctx->sw_lab.p;
+  sink.idx = (int64_t*)ctx->loo_idx.p;
+  sink.dist = (double*)ctx->loo_dist.p;
+  sink.flags = (int32_t*)ctx->loo_flags.p;
+  sink.tie_defer = 1;
+  const int W = (int)std::min<int64_t>((int64_t)kmax + 2, t.n);
+  rc = k1 > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
+                  : knn_run_search(ctx, dQ, m, W, metric, sink, s);
+  if (rc) return rc;
+  Sink out = sink;  // the rows of the reduced sets, at kmax
+  out.k = kmax;
+  out.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
+  out.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
+  out.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
+  launch_loo_drop(sink.dist, sink.idx, sink.flags, d_excl, m, kmax, t.lab, ctx->idx_off, t.n,
+                  out.dist, out.idx, out.flags, ctx->cu_count, s);
+  if (ctx->tune.ties) {  // the sweep's tie scan; std::sort over each query's remaining records
+    out.tie_mode = ctx->tune.ties;
+    TieScratch ts;
+    if ((rc = tie_setup(ctx, m, out, ts, true, s))) return rc;
+    launch_sweep_tie_scan(out.dist, out.idx, out.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
+                          out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
+    tie_order(ctx, ts, metric, dQ, out, s, d_excl);
+  }
+  launch_sweep_vote(out.idx, m, kmax, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
+                    (unsigned long long*)d_correct, ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+  return KNN_OK;
+}
+
+int knn_loo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                         int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                         double* d_dist, int32_t* d_flags, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-one-out sweep before set_train");
+  const TrainDev& t = ctx->train;
+  if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
+    return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
+                                     std::to_string(row0) + " + " + std::to_string(rows) +
+                                     ") outside the train set [0, " + std::to_string(t.n) + ")");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = ctx->loo_excl.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int64_t)))) return rc;
+  int64_t* excl = (int64_t*)ctx->loo_excl.p;
+  launch_loo_self(excl, rows, ctx->idx_off + row0, s);  // query i is train row row0 + i
+  HIP_TRY(hipGetLastError());
+  return knn_classify_sweep_excl_device(ctx, t.X64 + row0 * t.d, rows, excl, ks, nk, metric,
+                                        d_labels, d_correct ? t.lab + row0 : nullptr, d_correct,
+                                        d_idx, d_dist, d_flags, s);
+}
+
+int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
+                  int64_t* out_correct, int64_t* out_idx, double* out_dist, int32_t* out_flags) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
+  const int64_t n = ctx->train.n;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
+  if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  // fixed batches: the workspace does not grow with n
+  const int64_t B = std::min<int64_t>(n, 16384);
+  const int64_t nb = (n + B - 1) / B;
+  const size_t bk = (size_t)B * std::max(kmax, 1);
+  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
+  if (out_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
+  hipStream_t s = ctx->stream;
+  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);  // per batch, summed at the end
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t r0 = b * B, rows = std::min(B, n - r0);
+    rc = knn_loo_sweep_device(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
+                              out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
+                              out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
+                              out_dist ? (double*)ctx->o_dist.p : nullptr,
+                              (int32_t*)ctx->o_flags.p, s);
+    if (rc) return rc;
+    // the batch's labels [nk][rows] -> columns [r0, r0 + rows) of [nk][n]
+    HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
+                             (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                             (size_t)nk, hipMemcpyDeviceToHost, s));
+    if (out_correct)
+      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, s));
+    if (out_flags)
+      HIP_TRY(hipMemcpyAsync(out_flags + r0, ctx->o_flags.p, (size_t)rows * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, s));
+    if (out_idx && kmax > 0)
+      HIP_TRY(hipMemcpyAsync(out_idx + r0 * kmax, ctx->o_idx.p,
+                             (size_t)rows * kmax * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (out_dist && kmax > 0)
+      HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
+                             (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_correct)
+    for (int32_t j = 0; j < nk; j++) {
+      out_correct[j] = 0;
+      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
+    }
   return KNN_OK;
 }
 

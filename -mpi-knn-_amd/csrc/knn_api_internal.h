@@ -96,6 +96,9 @@ struct knn_ctx {
   // K sweep: the list of K, the search's label / idx / dist / flags at kmax,
   // host-API staging of labels [nk][m], truth [m] and correct counts [nk]
   DevBuf sw_ks, sw_lab, sw_idx, sw_dist, sw_flags, sw_out, sw_truth, sw_corr;
+  // K sweep under exclusion: the search's rows / flags at kmax + 1, the
+  // exclusions of a leave-one-out batch (and the host twin's staging)
+  DevBuf loo_idx, loo_dist, loo_flags, loo_excl;
   // host-API outputs
   DevBuf o_lab, o_idx, o_dist, o_flags;
   // normalisation: per-thread partial max/min, bounds, host-API staging
@@ -108,7 +111,7 @@ struct knn_ctx {
             &rescan_mask, &rescan_nkeep, &rescan_qc8, &rescan_t8, &smp_x64, &smp_xl2, &smp_img, &smp_scr, &smp_v, &smp_i,
             &ord_cent, &ord_cnorm, &ord_img, &ord_rank, &ord_rstart, &ord_perm, &ord_ipos, &ord_key, &ord_bcnt, &ord_tot,
             &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
-            &sw_out, &sw_truth, &sw_corr};
+            &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl};
   }
 };
 

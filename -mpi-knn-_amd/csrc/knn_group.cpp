@@ -923,6 +923,73 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
   return finish();
 }
 
+// Leave-one-out K sweep (knn_loo.hip): in mode 0 every rank holds the whole
+// train set, so rank r sweeps train rows [n r / G, n (r + 1) / G) of its own
+// copy in batches of at most 16384 rows (fixed workspace).
+int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                        int32_t* out_labels, int64_t* out_correct) {
+  if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group leave-one-out sweep before set_train");
+  if (g->mode == 1)
+    return knn_fail(KNN_ERR_ARG,
+                    "the leave-one-out sweep is not served in the train-sharded mode (mode 1): "
+                    "use a query-sharded group (mode 0)");
+  if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  if (metric != KNN_METRIC_L2 && metric != KNN_METRIC_L1)
+    return knn_fail(KNN_ERR_ARG, "metric must be 0 (L2) or 1 (L1)");
+  int rc;
+  int32_t kmax = 0;
+  const int64_t n = g->n;
+  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
+  const int G = g->ndev;
+  const int64_t B = 16384;
+  // per rank and batch: the correct counts, summed on the host at the end
+  std::vector<std::vector<int64_t>> hc(G);
+  for (int i = 0; i < G; i++) {
+    const int64_t r0 = n * i / G, r1 = n * (i + 1) / G;
+    HIP_G(hipSetDevice(g->devs[i]));
+    hipStream_t s = g->ctx[i]->stream;
+    HIP_G(hipEventRecord(g->ev0[i], s));
+    const int64_t nb = (r1 - r0 + B - 1) / B;
+    if (out_correct) hc[i].assign((size_t)nb * nk, 0);
+    if (nb > 0) {
+      const size_t bm = (size_t)std::min(B, r1 - r0);
+      if ((rc = g->slab[i].ensure(bm * nk * sizeof(int32_t)))) return rc;
+      if ((rc = g->scorr[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
+    }
+    for (int64_t b = 0; b < nb; b++) {
+      const int64_t q0 = r0 + b * B, rows = std::min(B, r1 - q0);
+      if ((rc = knn_loo_sweep_device(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
+                                     out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
+                                     nullptr, nullptr, s)))
+        return rc;
+      HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)n * sizeof(int32_t), g->slab[i].p,
+                             (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                             (size_t)nk, hipMemcpyDeviceToHost, s));
+      if (out_correct)
+        HIP_G(hipMemcpyAsync(hc[i].data() + b * nk, g->scorr[i].p, (size_t)nk * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, s));
+    }
+    HIP_G(hipEventRecord(g->ev1[i], s));
+  }
+  double span = 0.0;
+  for (int i = 0; i < G; i++) {
+    HIP_G(hipSetDevice(g->devs[i]));
+    if (int e = sync_rank(g, i, "leave-one-out sweep")) return e;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, g->ev0[i], g->ev1[i]) == hipSuccess)
+      span = std::max(span, (double)ms * 1e-3);
+  }
+  g->last_compute = span;
+  g->last_ties = 0;
+  if (out_correct)
+    for (int32_t j = 0; j < nk; j++) {
+      out_correct[j] = 0;
+      for (int i = 0; i < G; i++)
+        for (size_t b = 0; b * nk < hc[i].size(); b++) out_correct[j] += hc[i][b * nk + j];
+    }
+  return KNN_OK;
+}
+
 double knn_group_last_compute_seconds(knn_group* g) { return g ? g->last_compute : -1.0; }
 
 int64_t knn_group_last_tie_count(knn_group* g) { return g ? g->last_ties : -1; }

@@ -334,9 +334,26 @@ void launch_prep_i8_queries(const double* Q64, const double* mu, double scale, i
 constexpr int kFlagTieRef = 32;  // KNN_FLAG_TIE_REF: order resolved as the reference's
 int64_t tie_scratch_bytes(int64_t n, int class_cnt);
 // totals: device running count of the queries re-ordered (nullable)
+// excl (nullable, [m] global indices): query q's std::sort runs over the n - 1
+// records left when train row excl[q] is taken out (knn_loo.hip; a value
+// outside [idx_off, idx_off + n) excludes nothing); null: exactly the pass
+// without it
 void launch_tie_order(int metric, const TrainDev& t, const double* Q64, const int* tie_q,
                       const int* tie_cnt, int class_cnt, unsigned char* scratch, int64_t per_wg,
-                      int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s);
+                      int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s,
+                      const int64_t* excl = nullptr);
+// K sweep under exclusion (knn_loo.hip): compacts the search's rows at kmax + 1
+// (in_dist / in_idx [m][kmax + 1], in_flags [m]) into [m][kmax] rows without
+// train row excl[q] (global index; excl null or a value outside [idx_base,
+// idx_base + n): nothing excluded) and the flags of a kmax search on the
+// reduced set (TIE_BOUNDARY / TIE_VOTE / TIE_ORDER; EXACT_RESCAN / NONFINITE
+// carried over).  lab[idx - idx_base]: the entries' labels; cus sizes the grid.
+void launch_loo_drop(const double* in_dist, const int64_t* in_idx, const int32_t* in_flags,
+                     const int64_t* excl, int64_t m, int kmax, const int32_t* lab,
+                     int64_t idx_base, int64_t n, double* out_dist, int64_t* out_idx,
+                     int32_t* out_flags, int cus, hipStream_t s);
+// excl[i] = first + i (leave-one-out: query i is train row first + i)
+void launch_loo_self(int64_t* excl, int64_t rows, int64_t first, hipStream_t s);
 // K sweep (knn_sweep.hip): the reference's label at every K of a list from
 // one ordered top-kmax row per query (kmax >= every K).  ks: device array of
 // nk values in the caller's order (duplicates allowed); lab[idx - idx_base] is

@@ -1728,7 +1728,8 @@ template <int METRIC>
 __global__ void __launch_bounds__(kTieThreads)
 tie_order_kernel(TrainDev t, const double* __restrict__ Q64, const int* __restrict__ tie_q,
                  const int* __restrict__ tie_cnt, int class_cnt, unsigned char* __restrict__ scratch,
-                 int64_t per_wg, Sink sink, unsigned long long* totals) {
+                 int64_t per_wg, Sink sink, unsigned long long* totals,
+                 const int64_t* __restrict__ excl) {
   __shared__ double tiles[kTieThreads / 64][64 * (kFullDC + 1)];
   __shared__ RefSortShared s;
   const int count = *tie_cnt;
@@ -1743,10 +1744,24 @@ tie_order_kernel(TrainDev t, const double* __restrict__ Q64, const int* __restri
   int* cnt = Rb + n;
   for (int i = blockIdx.x; i < count; i += gridDim.x) {
     const int64_t q = tie_q[i];
-    exact_all_dist<METRIC>(t, Q64 + q * t.d, D, tiles[threadIdx.x >> 6]);
-    for (int64_t j = threadIdx.x; j < n; j += kTieThreads) P[j] = (int)j;
+    // K sweep under exclusion (knn_loo.hip): the reference's std::sort over the
+    // n - 1 records left without local row e, filled in row order -- rows
+    // [0, e) at their own positions, rows (e, n) one position down
+    // (exact_rows_dist writes D[absolute row]) -- record j being row j + (j >= e)
+    int64_t e = excl ? excl[q] - sink.idx_off : -1;
+    if (e < 0 || e >= n) e = -1;
+    int64_t nr = n;
+    if (e < 0) {
+      exact_all_dist<METRIC>(t, Q64 + q * t.d, D, tiles[threadIdx.x >> 6]);
+      for (int64_t j = threadIdx.x; j < n; j += kTieThreads) P[j] = (int)j;
+    } else {
+      nr = n - 1;
+      exact_rows_dist<METRIC>(t, Q64 + q * t.d, 0, e, D, tiles[threadIdx.x >> 6]);
+      exact_rows_dist<METRIC>(t, Q64 + q * t.d, e + 1, n, D - 1, tiles[threadIdx.x >> 6]);
+      for (int64_t j = threadIdx.x; j < nr; j += kTieThreads) P[j] = (int)(j + (j >= e));
+    }
     __syncthreads();
-    ref_sort_prefix(D, P, Lb, Rb, (int)n, sink.k, s);
+    ref_sort_prefix(D, P, Lb, Rb, (int)nr, sink.k, s);
     ref_finish(q, D, P, sink.k, t.lab, sink.idx_off, class_cnt, cnt, sink);
   }
 }
@@ -1832,14 +1847,15 @@ void launch_tie_resolve(const double* D, const PartRows& pr, int nsel, const int
 
 void launch_tie_order(int metric, const TrainDev& t, const double* Q64, const int* tie_q,
                       const int* tie_cnt, int class_cnt, unsigned char* scratch, int64_t per_wg,
-                      int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s) {
+                      int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s,
+                      const int64_t* excl) {
   if (nwg <= 0) return;
   if (metric == 0)
     hipLaunchKernelGGL(tie_order_kernel<0>, dim3(nwg), dim3(kTieThreads), 0, s, t, Q64, tie_q,
-                       tie_cnt, class_cnt, scratch, per_wg, sink, totals);
+                       tie_cnt, class_cnt, scratch, per_wg, sink, totals, excl);
   else
     hipLaunchKernelGGL(tie_order_kernel<1>, dim3(nwg), dim3(kTieThreads), 0, s, t, Q64, tie_q,
-                       tie_cnt, class_cnt, scratch, per_wg, sink, totals);
+                       tie_cnt, class_cnt, scratch, per_wg, sink, totals, excl);
 }
 
 // ------------------------------------------------ large k (k > kMaxK)

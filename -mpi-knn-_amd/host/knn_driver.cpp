@@ -20,6 +20,10 @@
 // accuracy strictly exceeds the running best (the reference's first-to-exceed
 // idiom, cpp:332-335), prints "selected K = <k>" and the reference's
 // "accuracy = <acc>" line for it, and runs the test pass at that K.
+// --loo (needs --K_list; no validation file is read): the validation pass is
+// replaced by a leave-one-out sweep of the train set (knn_group_loo_sweep:
+// every train row classified against all the others), prints "K = <k> loo
+// accuracy = <acc>" per K, selects K the same way and runs the test pass.
 // The timed region spans the same work as the reference (barrier to
 // barrier: CSV parsing, distribution, normalisation, both passes, output).
 #include <chrono>
@@ -54,6 +58,7 @@ struct Config {
   int threads = 0;
   bool timings = false;
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
+  bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
 };
 
 bool parse_bool(const std::string& v) { return v == "true" || v == "1" || v == "yes"; }
@@ -64,9 +69,11 @@ void usage() {
           "  [--class_cnt C] [--Euclidean_distance true|false] [--Normalize true|false]\n"
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
-          "  [--threads T] [--timings] [--K_list K1,K2,...]\n"
+          "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo]\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
-          "  set; the test pass runs at the first K with the best accuracy\n");
+          "  set; the test pass runs at the first K with the best accuracy\n"
+          "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
+          "  (no validation file is read)\n");
 }
 
 // "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit
@@ -98,6 +105,7 @@ int parse_args(int argc, char** argv, Config& c) {
     if (eq != std::string::npos) { v = a.substr(eq + 1); a = a.substr(0, eq); }
     else if (a == "strict") { c.strict = true; continue; }
     else if (a == "timings") { c.timings = true; continue; }
+    else if (a == "loo") { c.loo = true; continue; }
     else if (i + 1 < argc) v = argv[++i];
     else { usage(); return 1; }
     if (a == "dim") c.dim = atoi(v.c_str());
@@ -117,6 +125,7 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "mode") c.mode = (v == "train" || v == "1") ? 1 : 0;
     else if (a == "strict") c.strict = parse_bool(v);
     else if (a == "threads") c.threads = atoi(v.c_str());
+    else if (a == "loo") c.loo = parse_bool(v);
     else if (a == "K_list") {
       if (!parse_k_list(v, c.K_list)) {
         fprintf(stderr, "--K_list takes a comma-separated list of non-negative integers\n");
@@ -155,15 +164,22 @@ int main(int argc, char** argv) {
   if (c.gpus < 1) die("--gpus must be >= 1");
   if (c.dim <= 0 || c.K < 0 || c.N_train <= 0 || c.N_test < 0 || c.N_val < 0 || c.class_cnt <= 0)
     die("bad configuration");
+  if (c.loo && c.K_list.empty()) die("--loo needs --K_list (the K to judge by leave-one-out)");
+  if (c.loo) c.Validation = false;  // the train set is its own validation set: no file is read
   if (c.strict && (c.N_train % c.gpus || c.N_test % c.gpus || (c.Validation && c.N_val % c.gpus)))
     die("N_train/N_test/N_val not divisible by the number of GPUs (--strict, cpp:127-129)");
   if (!c.K_list.empty()) {
-    if (!c.Validation) die("--K_list needs --Validation true (K is judged on the validation set)");
-    if (c.N_val <= 0) die("--K_list needs a validation set (N_val > 0)");
+    if (!c.loo && !c.Validation)
+      die("--K_list needs --Validation true (K is judged on the validation set)");
+    if (!c.loo && c.N_val <= 0) die("--K_list needs a validation set (N_val > 0)");
     if (c.K_list.size() > 4096) die("--K_list takes at most 4096 values");
-    for (size_t i = 0; i < c.K_list.size(); i++)
+    for (size_t i = 0; i < c.K_list.size(); i++) {
       if (c.K_list[i] > c.N_train)
         die("--K_list entry " + std::to_string(c.K_list[i]) + " exceeds N_train");
+      if (c.loo && c.K_list[i] > c.N_train - 1)
+        die("--K_list entry " + std::to_string(c.K_list[i]) +
+            " exceeds N_train - 1 (--loo takes the row itself out)");
+    }
   }
 
   knn_group* g = nullptr;
@@ -201,7 +217,25 @@ int main(int argc, char** argv) {
   phase("set_train");
   const int metric = c.Euclidean_distance ? KNN_METRIC_L2 : KNN_METRIC_L1;
 
-  if (!c.K_list.empty()) {  // the validation pass (cpp:308-349) for every K of the list
+  if (c.loo) {  // cpp:308-349 with every train row judged against all the others
+    const int32_t nk = (int32_t)c.K_list.size();
+    std::vector<int32_t> pred((size_t)nk * c.N_train);
+    std::vector<int64_t> correct(nk, 0);
+    if (knn_group_loo_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data()))
+      die(knn_last_error());
+    double best = -1.0;
+    for (int32_t i = 0; i < nk; i++) {
+      double acc = (double)correct[i];  // acc_calc, cpp:69-84
+      acc /= c.N_train;
+      std::cout << "K = " << c.K_list[i] << " loo accuracy = " << acc << std::endl;
+      if (acc > best) {  // first to strictly exceed, like cpp:332-335
+        best = acc;
+        c.K = c.K_list[i];
+      }
+    }
+    std::cout << "selected K = " << c.K << std::endl;
+    phase("loo");
+  } else if (!c.K_list.empty()) {  // the validation pass (cpp:308-349) for every K of the list
     const int32_t nk = (int32_t)c.K_list.size();
     std::vector<int32_t> pred((size_t)nk * c.N_val);
     std::vector<int64_t> correct(nk, 0);

@@ -40,7 +40,8 @@ EXPORTED = (
     "knn_shard_distances_device", "knn_tie_resolve_device", "knn_group_transport",
     "knn_group_last_tie_count", "knn_group_set_precision", "knn_group_set_tuning",
     "knn_vote_sweep_device", "knn_classify_sweep_device", "knn_classify_sweep",
-    "knn_group_classify_sweep",
+    "knn_group_classify_sweep", "knn_classify_sweep_excl_device", "knn_loo_sweep_device",
+    "knn_loo_sweep", "knn_group_loo_sweep",
 )
 GROUP_RCCL = 0x100  # knn_group_create mode flag: RCCL collectives also at one GPU
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1, 2
@@ -140,6 +141,11 @@ def lib():
                                       ctypes.c_int),
         "knn_classify_sweep": ([P, P, i64, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
         "knn_group_classify_sweep": ([P, P, i64, P, i32, i32, P, P, P], ctypes.c_int),
+        "knn_classify_sweep_excl_device": ([P, P, i64, P, P, i32, i32, P, P, P, P, P, P, P],
+                                           ctypes.c_int),
+        "knn_loo_sweep_device": ([P, i64, i64, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
+        "knn_loo_sweep": ([P, P, i32, i32, P, P, P, P, P], ctypes.c_int),
+        "knn_group_loo_sweep": ([P, P, i32, i32, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -233,24 +239,33 @@ class Classifier:
             return labels, idx[:, :k], dist[:, :k], flags
         return labels
 
-    def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False):
+    def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False, exclude=None):
         """Labels for every K of `ks` (any order, duplicates allowed) from one
         search at max(ks): labels int32[nk, m], row i for ks[i].  With `truth`
         (int32[m]) also correct int64[nk] = (labels[i] == truth).sum().  With
-        return_neighbors also (idx[m, kmax], dist[m, kmax], flags[m])."""
+        return_neighbors also (idx[m, kmax], dist[m, kmax], flags[m]).
+        `exclude` (int64[m], global train indices, -1 = none): query i is
+        answered as if train row exclude[i] were not in the train set
+        (knn_classify_sweep_excl_device; staged through torch device tensors);
+        then every K <= n_train - 1."""
         Q = _f64(Q)
         m = Q.shape[0]
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
         nk = ks.shape[0]
         kmax = int(ks.max()) if nk else 0
-        labels = np.empty((nk, m), np.int32)
-        flags = np.empty(m, np.int32)
-        idx = np.empty((m, max(kmax, 1)), np.int64) if return_neighbors else None
-        dist = np.empty((m, max(kmax, 1)), np.float64) if return_neighbors else None
         if truth is not None:
             truth = np.ascontiguousarray(truth, dtype=np.int32)
             if truth.shape != (m,):
                 raise ValueError("truth must have one label per query")
+        if exclude is not None:
+            exclude = np.ascontiguousarray(exclude, dtype=np.int64)
+            if exclude.shape != (m,):
+                raise ValueError("exclude must have one train index (or -1) per query")
+            return self._sweep_excl(Q, exclude, ks, kmax, metric, truth, return_neighbors)
+        labels = np.empty((nk, m), np.int32)
+        flags = np.empty(m, np.int32)
+        idx = np.empty((m, max(kmax, 1)), np.int64) if return_neighbors else None
+        dist = np.empty((m, max(kmax, 1)), np.float64) if return_neighbors else None
         correct = np.zeros(nk, np.int64) if truth is not None else None
         _check(lib().knn_classify_sweep(self._h, _ptr(Q), m, _ptr(ks), nk, int(metric),
                                         _ptr(labels), _ptr(truth), _ptr(correct), _ptr(idx),
@@ -260,10 +275,72 @@ class Classifier:
             out += (idx[:, :kmax], dist[:, :kmax], flags)
         return out[0] if len(out) == 1 else out
 
-    def classify_sweep_device(self, dQ_ptr, m, ks, metric, d_labels, d_truth=None,
-                              d_correct=None, d_idx=None, d_dist=None, d_flags=None, stream=None):
-        """Device-pointer sweep (enqueue only); ks is a host sequence."""
+    def _sweep_excl(self, Q, exclude, ks, kmax, metric, truth, return_neighbors):
+        import torch
+        dev = torch.device("cuda", self.device)
+        m, nk = Q.shape[0], ks.shape[0]
+        dQ = torch.from_numpy(Q).to(dev)
+        dE = torch.from_numpy(exclude).to(dev)
+        dT = torch.from_numpy(truth).to(dev) if truth is not None else None
+        dL = torch.empty((nk, m), dtype=torch.int32, device=dev)
+        dC = torch.zeros(nk, dtype=torch.int64, device=dev) if truth is not None else None
+        dF = torch.empty(m, dtype=torch.int32, device=dev)
+        dI = torch.empty((m, max(kmax, 1)), dtype=torch.int64, device=dev) if return_neighbors else None
+        dD = torch.empty((m, max(kmax, 1)), dtype=torch.float64, device=dev) if return_neighbors else None
+        torch.cuda.synchronize(dev)  # the context's stream is not torch's
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.classify_sweep_device(p(dQ), m, ks, metric, p(dL), p(dT), p(dC), p(dI), p(dD), p(dF),
+                                   d_excl=p(dE))
+        self.sync()
+        out = (dL.cpu().numpy(),)
+        if truth is not None:
+            out += (dC.cpu().numpy(),)
+        if return_neighbors:
+            out += (dI.cpu().numpy()[:, :kmax], dD.cpu().numpy()[:, :kmax], dF.cpu().numpy())
+        return out[0] if len(out) == 1 else out
+
+    def loo_sweep(self, ks, metric=L2, return_neighbors=False):
+        """Leave-one-out K sweep over the whole train set (knn_loo_sweep): every
+        train row classified against all the OTHER train rows at every K of
+        `ks` (each <= n_train - 1).  Returns (labels int32[nk, n], correct
+        int64[nk]) and with return_neighbors also (idx[n, kmax], dist[n, kmax],
+        flags[n]); accuracy at ks[i] = correct[i] / n."""
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk, n = ks.shape[0], self.n_train
+        kmax = int(ks.max()) if nk else 0
+        labels = np.empty((nk, n), np.int32)
+        correct = np.zeros(nk, np.int64)
+        flags = np.empty(n, np.int32)
+        idx = np.empty((n, max(kmax, 1)), np.int64) if return_neighbors else None
+        dist = np.empty((n, max(kmax, 1)), np.float64) if return_neighbors else None
+        _check(lib().knn_loo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(labels),
+                                   _ptr(correct), _ptr(idx), _ptr(dist), _ptr(flags)))
+        if return_neighbors:
+            return labels, correct, idx[:, :kmax], dist[:, :kmax], flags
+        return labels, correct
+
+    def loo_sweep_device(self, row0, rows, ks, metric, d_labels, d_correct=None, d_idx=None,
+                         d_dist=None, d_flags=None, stream=None):
+        """Leave-one-out sweep of train rows [row0, row0 + rows) into device
+        buffers (enqueue only): d_labels [nk][rows], d_correct [nk]."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_loo_sweep_device(self._h, int(row0), int(rows), _ptr(ks), ks.shape[0],
+                                          int(metric), d_labels, d_correct, d_idx, d_dist, d_flags,
+                                          stream))
+
+    def classify_sweep_device(self, dQ_ptr, m, ks, metric, d_labels, d_truth=None,
+                              d_correct=None, d_idx=None, d_dist=None, d_flags=None, stream=None,
+                              d_excl=None):
+        """Device-pointer sweep (enqueue only); ks is a host sequence.  d_excl
+        (device int64[m], global train indices, -1 = none): the sweep under
+        exclusion (knn_classify_sweep_excl_device)."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        if d_excl is not None:
+            _check(lib().knn_classify_sweep_excl_device(self._h, dQ_ptr, m, d_excl, _ptr(ks),
+                                                        ks.shape[0], int(metric), d_labels,
+                                                        d_truth, d_correct, d_idx, d_dist,
+                                                        d_flags, stream))
+            return
         _check(lib().knn_classify_sweep_device(self._h, dQ_ptr, m, _ptr(ks), ks.shape[0],
                                                int(metric), d_labels, d_truth, d_correct, d_idx,
                                                d_dist, d_flags, stream))
@@ -407,6 +484,7 @@ class Group:
         self._h = ctypes.c_void_p()
         arr = (ctypes.c_int * len(devices))(*devices)
         flags = GROUP_RCCL if rccl else 0
+        self.n_train = 0
         _check(lib().knn_group_create(ctypes.byref(self._h), len(devices), arr, int(mode) | flags))
 
     def transport(self):
@@ -437,6 +515,7 @@ class Group:
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         n, d = X.shape
         _check(lib().knn_group_set_train(self._h, _ptr(X), _ptr(labels), n, d, int(class_cnt)))
+        self.n_train = n
 
     def classify(self, Q, k, metric=L2, return_neighbors=False):
         Q = _f64(Q)
@@ -468,6 +547,17 @@ class Group:
                                               _ptr(labels), _ptr(truth), _ptr(correct)))
         return labels if truth is None else (labels, correct)
 
+    def loo_sweep(self, ks, metric=L2):
+        """Classifier.loo_sweep over the group (mode 0; mode 1 raises KnnError):
+        labels int32[nk, n] in train row order, correct int64[nk]."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk = ks.shape[0]
+        labels = np.empty((nk, self.n_train), np.int32)
+        correct = np.zeros(nk, np.int64)
+        _check(lib().knn_group_loo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(labels),
+                                         _ptr(correct)))
+        return labels, correct
+
     def last_compute_seconds(self):
         return float(lib().knn_group_last_compute_seconds(self._h))
 
@@ -484,7 +574,9 @@ def run_driver(cfg: KnnConfig, workdir, gpus=1, mode="query", extra=()):
     `extra` takes further driver flags, e.g. ["--K_list", "1,3,5"] (needs
     Validation: one search scores every K on the validation set, prints
     "K = <k> accuracy = <acc>" per K and "selected K = <k>", and the test
-    pass runs at the selected K)."""
+    pass runs at the selected K), or ["--loo", "--K_list", "1,3,5"] (no
+    validation file: every K is scored by leave-one-out on the train set,
+    "K = <k> loo accuracy = <acc>" per K)."""
     if not os.path.exists(DRIVER_PATH):
         raise KnnError("driver not built: " + DRIVER_PATH)
     args = [DRIVER_PATH]

@@ -185,6 +185,52 @@ int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* 
                        int64_t* out_correct, int64_t* out_idx, double* out_dist,
                        int32_t* out_flags);
 
+/* ---- K sweep under exclusion / leave-one-out: score every K on the train
+ * set itself.  The reference judges K on a separate validation CSV
+ * (Validation, cpp:308-343); classifying the train rows against themselves
+ * instead finds every row at distance 0 (K = 1 scores 100 %).  These calls
+ * take one train row out of a query's neighbour search.  One rule fixes every
+ * output: for a query with excluded global train index e the result is what
+ * knn_classify_sweep returns on a context whose train set is the current one
+ * WITH ROW e REMOVED (labels lose the same entry), reported indices >= e
+ * shifted back up by one so every index refers to the full train set.  That
+ * covers the label at every K, the neighbour indices, their order and the
+ * distances, the flag bits KNN_FLAG_TIE_BOUNDARY | TIE_VOTE | TIE_ORDER |
+ * TIE_REF and the rows "ties" = 0 / 1 / 2 re-order: the order among equal
+ * distances is the reference's std::sort over the n - 1 remaining records
+ * (cpp:323), another introsort run than the one over all n.
+ * KNN_FLAG_EXACT_RESCAN may differ (certification is not part of the
+ * contract).  One search at max(ks) + 1 serves the call.
+ *
+ * knn_classify_sweep_excl_device: knn_classify_sweep_device plus d_excl [m]
+ * (device, global indices as reported in d_idx, i.e. with the train set's
+ * idx_offset; -1 = exclude nothing: that query equals the plain sweep's).  A
+ * value outside {-1} and [idx_offset, idx_offset + n_train) is treated as -1.
+ * d_excl NULL = none for all queries (the plain sweep).  With d_excl non-NULL
+ * ks[i] <= n_train - 1 (KNN_ERR_ARG names the offending entry).  Enqueue only. */
+int knn_classify_sweep_excl_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                   const int64_t* d_excl, const int32_t* ks, int32_t nk,
+                                   int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                   int64_t* d_correct, int64_t* d_idx, double* d_dist,
+                                   int32_t* d_flags, void* stream);
+/* Leave-one-out over train rows [row0, row0 + rows) of the context (local row
+ * numbers; KNN_ERR_ARG for a range outside [0, n_train]): the queries are the
+ * context's own fp64 train rows, query i excludes global index idx_offset +
+ * row0 + i and its truth is the label of row row0 + i (≙ Val_label against
+ * Val_label_buffer, cpp:341-343).  d_labels [nk*rows] required; d_correct
+ * [nk] nullable; d_idx / d_dist [rows*kmax], d_flags [rows] nullable.
+ * 0 <= ks[i] <= n_train - 1.  Enqueue only. */
+int knn_loo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                         int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                         double* d_dist, int32_t* d_flags, void* stream);
+/* Host twin over all n_train rows (waits for the result): out_labels [nk][n]
+ * required, out_correct [nk] (the leave-one-out cnt of cpp:341-343 per K),
+ * out_idx / out_dist [n*kmax], out_flags [n] nullable.  Runs
+ * knn_loo_sweep_device over fixed batches of at most 16384 rows, so the
+ * workspace does not grow with n; out_correct is summed over the batches. */
+int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
+                  int64_t* out_correct, int64_t* out_idx, double* out_dist, int32_t* out_flags);
+
 /* Train-sharded building block: exact top-w of THIS context's shard for
  * each query, sorted by (dist, global idx), with each neighbour's label.
  * Rows beyond the shard size are padded with dist=+inf, idx=-1, label=-1.
@@ -408,6 +454,14 @@ int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int3
 int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
                              int32_t nk, int32_t metric, int32_t* out_labels,
                              const int32_t* truth, int64_t* out_correct);
+/* Leave-one-out K sweep over the group (see knn_loo_sweep; cpp:308-343 with
+ * the train set as its own validation set): out_labels [nk][n] in train row
+ * order, out_correct [nk] (nullable).  mode 0: rank r takes rows [n r / G,
+ * n (r + 1) / G) of the train set every rank holds, in batches of at most
+ * 16384 rows; the host sums out_correct.  mode 1 (train-sharded): not served,
+ * KNN_ERR_ARG with a message saying so. */
+int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                        int32_t* out_labels, int64_t* out_correct);
 /* Seconds of the last group classify spent between the first enqueue and
  * the last device completion (device-resident inputs, excludes H2D/D2H). */
 double knn_group_last_compute_seconds(knn_group* g);
