@@ -389,14 +389,15 @@ static int ensure_fp16(knn_ctx* ctx, hipStream_t s) {
   return KNN_OK;
 }
 
-// The int8 image for kernel metrics 5 / 6 (knn_prep.hip): codes x 2^s - c of
-// every row (16-B chunks swizzled as the fp16 image for metric 5, plain for
+// The int8 image for kernel metrics 5 / 6 / 7 (knn_prep.hip): codes x 2^s - c
+// of every row (16-B chunks swizzled as the fp16 image for metric 5, plain for
 // metric 6) + the accumulator seeds -ceil(||k||^2 / 2); rows of DP + 16
-// bytes, n_pad rows.
+// bytes, n_pad rows.  Metric 7 (L1 on the codes) reads metric 6's image, its
+// codes only; the fp32 image of set_train stays for the rescan's filter.
 static int ensure_i8(knn_ctx* ctx, int kmetric, hipStream_t s) {
   const TrainDev& t = ctx->train;
-  const int DPi = kmetric == 6 ? pad_dim_i8w(t.d) : pad_dim_i8(t.d);
-  const int swz = kmetric == 6 ? 0 : 1;
+  const int DPi = kmetric >= 6 ? pad_dim_i8w(t.d) : pad_dim_i8(t.d);
+  const int swz = kmetric >= 6 ? 0 : 1;
   if (!ctx->i8_ok || DPi <= 0) return knn_fail(KNN_ERR_ARG, "train set not integer-coded (int8 pass)");
   if (ctx->DPi == DPi && ctx->i8_swz == swz) return KNN_OK;
   int rc;
@@ -845,8 +846,12 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
     t8.DP = DP;
     launch_merge_rerank(metric, (const float*)ctx->cand_v.p, (const int*)ctx->cand_i.p, NL, R, t8,
                         dQ, m, W, C, 0.0,
-                        ProxyScale{qvalid, 0.0, 1.0 / DP, false, (const double*)ctx->i8_cent.p, qpos,
-                                   (const signed char*)ctx->XI.p, DP + 16, DP, p.i8_swz},
+                        // (metric 7: L1 proxies are exact on the grid and void off it;
+                        // the re-rank reads the fp64 rows)
+                        kmetric == 7
+                            ? ProxyScale{qvalid, 0.0, 0.0, false, (const double*)ctx->i8_cent.p, qpos}
+                            : ProxyScale{qvalid, 0.0, 1.0 / DP, false, (const double*)ctx->i8_cent.p, qpos,
+                                         (const signed char*)ctx->XI.p, DP + 16, DP, p.i8_swz},
                         cl.gthr, sink,
                         (int*)ctx->rescan_q.p, (double*)ctx->rescan_tau.p, (int*)ctx->rescan_cnt.p,
                         sm, rp, s);

@@ -106,7 +106,9 @@ int cand_queries_per_wave(int metric, int DP);  // resident kernel: queries per 
 
 // metric: 0 = L2 fp32 MFMA, 1 = L1 fp32 VALU, 2 = L2 bf16x3 MFMA (32x32x16),
 // 3 = L2 bf16x3 on 16x16x32, 4 = L2 fp16 on 16x16x32, 5 = L2 int8 on
-// 16x16x64, 6 = L2 int8 on 32x32x32 (see knn_cand_res.hip)
+// 16x16x64, 6 = L2 int8 on 32x32x32 (see knn_cand_res.hip), 7 = L1 on int8
+// codes, v_sad_u8 (knn_cand_sad.hip: X32 = metric 6's int8 image, Q32 = the
+// int8 query codes, xinit = xinit_l1)
 struct CandLaunch {
   int metric, DP, R, S, n_qt;
   int64_t n_pad;
@@ -161,6 +163,11 @@ void launch_prep_queries(const double* Q64, const double* mu, int64_t m, int d, 
                          int64_t m_pad, double scale, int jx, float* Q32, hipStream_t s);
 // false: no kernel instantiated for this (DP, R, metric, nw) -- nothing launched
 bool launch_cand(const CandLaunch& c, hipStream_t s);
+// kernel metric 7 (knn_cand_sad.hip; reached through launch_cand and the
+// cand_* queries above)
+bool launch_cand_sad(const CandLaunch& c, hipStream_t s);
+int sad_blocks_per_cu(int DP, int R, int nw);
+int sad_tile_rows(int DP);
 // gthr: the candidate kernel's per-query global thresholds ([m_pad][kGthrSlots] keys)
 // or null when the kernel kept none
 // failed queries are appended to rescan_q with rescan_tau = the W-th exact

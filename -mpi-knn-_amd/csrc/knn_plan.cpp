@@ -186,6 +186,23 @@ static bool use_i8(const PlanIn& in) {
   return in.m >= 4096 && in.W <= kQuadMaxW;
 }
 
+// L1 on int8 codes (kernel metric 7, knn_cand_sad.hip): integer-coded train
+// sets at d <= 256 under the L1 metric.  Tuning key "i8l1": 0 off, 1 on at
+// every batch size, -1 auto: use_i8's rule (AUTO precision, batches of >=
+// 4096 queries, W <= kQuadMaxW, until a batch sends more than 1/16 of its
+// queries to the rescan), gated by kI8L1Auto -- the pass beat the fp32 L1
+// kernel's whole call (prep + candidate + re-rank + rescan) far beyond the
+// run-to-run spread at both measured shapes: 1M x 10k, d = 128: 88.47-88.71
+// -> 11.80-11.83 ms; 40000 x 4096: 1.677-1.688 -> 0.415-0.432 ms
+// (profiles/ab_log.md, "l1sad").  "i8" (the L2 pass) does not reach it.
+constexpr bool kI8L1Auto = true;
+static bool use_i8l1(const PlanIn& in) {
+  if (in.metric != KNN_METRIC_L1 || !in.i8_ok || pad_dim_i8w(in.d) <= 0) return false;
+  if (in.tune.i8l1 >= 0) return in.tune.i8l1 > 0;
+  if (!kI8L1Auto || in.precision != KNN_PRECISION_AUTO || in.i8_off) return false;
+  return in.m >= 4096 && in.W <= kQuadMaxW;
+}
+
 static bool use_bf16x3(const PlanIn& in) {
   if (in.metric != KNN_METRIC_L2) return false;
   if (in.precision == KNN_PRECISION_FP32) return false;
@@ -196,6 +213,8 @@ static bool use_bf16x3(const PlanIn& in) {
 // (knn_cand_res.hip, res_variant, which refuses the launch of any other): a
 // variant build that instantiates more extends this with it.
 static bool resident_variant(int DP, int R, int M, int NW) {
+  // metric 7 (knn_cand_sad.hip): DP of pad_dim_i8w, R in {8, 16}, 4 or 8 waves
+  if (M == 7) return pad_dim_i8w(DP) == DP && (R == 8 || R == 16) && (NW == 4 || NW == 8);
   return (M != 2 || DP % 16 == 0) && (M != 1 || (NW == 4 && R != 4)) &&
          (M < 3 || (DP % 32 == 0 && (R == 4 || (M >= 5 && R == 8)) && (NW == 8 || M >= 4))) &&
          (NW != 16 || M == 4) && (M != 5 || (DP % 64 == 0 && (NW == 8 || NW == 4))) &&
@@ -241,7 +260,7 @@ static void choose_geometry(const PlanIn& in, SearchPlan& p) {
   if (p.s3q) S_hi = std::min(S_hi, kMaxUnion / (4 * 8));
   for (int R : {4, 8, 16}) {
     if (!list_len_ok(R)) continue;
-    if (R == 4 && (DP > 256 || metric == 1)) continue;
+    if (R == 4 && (DP > 256 || metric == 1 || metric == 7)) continue;
     const int64_t slots = (int64_t)(p.s3q ? in.facts.s3q_blocks_per_cu()
                                           : in.facts.cand_blocks_per_cu(metric, DP, R, p.nw)) *
                           in.cu_count;
@@ -314,7 +333,13 @@ SearchPlan plan_search(const PlanIn& in) {
   p.kmetric = in.metric;
   p.DP = in.DP;
   p.image = IMG_FP32;
-  if (use_i8(in)) {
+  if (use_i8l1(in)) {
+    // L1 on the codes of metric 6's plain int8 image, one list per lane as
+    // the fp32 L1 kernel
+    p.kmetric = 7;
+    p.image = IMG_I8;
+    p.DP = pad_dim_i8w(in.d);
+  } else if (use_i8(in)) {
     p.kmetric = i8_kernel_d(tune, in.d);
     p.image = IMG_I8;
     p.DP = p.kmetric == 6 ? pad_dim_i8w(in.d) : pad_dim_i8(in.d);
@@ -345,6 +370,8 @@ SearchPlan plan_search(const PlanIn& in) {
   // int8 32x32x32: 16 waves (512 queries per staged tile) only in builds
   // with KNN_I8W_NW16 (otherwise the launch is refused: no such kernel)
   else if (kmetric == 6 && tune.nw == 16) p.nw = 16;
+  // L1 on int8 codes: 4 or 8 (256 queries share each staged tile)
+  else if (kmetric == 7) p.nw = tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4);
   else if (kmetric >= 3) p.nw = 8;  // (the 16x16 layouts: fp16, bf16x3, int8)
   else if (DP <= 256 && kmetric != 1) p.nw = tune.nw ? std::min(tune.nw, 8) : (m >= 4096 ? 8 : 4);
   else p.nw = 4;
@@ -409,12 +436,15 @@ SearchPlan plan_search(const PlanIn& in) {
   p.gmask = p.gk ? p.G - 1 : 3;
   p.qblk = tune.qblk > 0 ? std::min(tune.qblk, p.n_qt) : 0;
   // region order of the queries (resident kernels, metrics 4-6; knn_order.hip)
-  p.query_order = in.ord_P > 0 && tune.order != 0 && !p.s3 && kmetric >= 4 && DP <= 256;
+  // (metric 7 takes its queries in call order and starts every stream at the
+  // split's first tile: a train set laid out by region or in norm blocks is
+  // just another row order to it -- lists carry image positions either way)
+  p.query_order = in.ord_P > 0 && tune.order != 0 && !p.s3 && kmetric >= 4 && kmetric != 7 && DP <= 256;
   p.ophase = std::min(tune.ophase < 0 ? kOrderPhases : tune.ophase, in.ord_P);
   // the int8 image's chunks are swizzled for the 16x16x64 kernel, plain for
   // 32x32x32; the fp16 image's as tuning "xhswz" says (only the metric 4 and
   // 5 kernels read xsw)
-  p.i8_swz = kmetric == 6 ? 0 : 1;
+  p.i8_swz = kmetric == 6 || kmetric == 7 ? 0 : 1;
   p.xsw = kmetric >= 5 ? p.i8_swz : tune.xhswz != 0;
   // the int8 rescan filter (metric 6's plain image; knn_select.hip)
   // (tuning key "i8resc": -1 / 1 auto, 0 every failed query on the fp32 filter)
@@ -432,14 +462,18 @@ SearchPlan plan_search(const PlanIn& in) {
   // the LAST call: it is armed by an fp16 call and dropped by any other
   // (a later fp16 call re-arms it with its own count)
   p.auto_arm = !p.abl && ((kmetric == 4 && in.precision == KNN_PRECISION_AUTO && tune.fp16 < 0) ||
-                          (kmetric >= 5 && tune.i8 < 0));
+                          ((kmetric == 5 || kmetric == 6) && tune.i8 < 0) ||
+                          (kmetric == 7 && tune.i8l1 < 0));
   p.ok = true;
   if (p.qres)
     snprintf(p.kernel, sizeof p.kernel, "cand_qres_kernel<%d>", DP / 32);
   else if (p.s3)
     snprintf(p.kernel, sizeof p.kernel, "cand_s3_kernel<%d,%s,%s>", p.R, p.s3h ? "true" : "false",
              p.s3q ? "true" : "false");
-  else if (DP <= 256) {
+  else if (kmetric == 7) {
+    snprintf(p.kernel, sizeof p.kernel, "cand_sad_kernel<%d,%d,%d>", DP, p.R, p.nw);
+    p.ok = resident_variant(DP, p.R, kmetric, p.nw);
+  } else if (DP <= 256) {
     snprintf(p.kernel, sizeof p.kernel, "cand_kernel<%d,%d,%d,%d>", DP, p.R, kmetric, p.nw);
     p.ok = cand_supported(DP) && resident_variant(DP, p.R, kmetric, p.nw);
   } else
@@ -461,6 +495,7 @@ SearchPlan plan_search(const PlanIn& in) {
 //     the operands themselves) and added by the merge with the seed's own
 //     rounding and the fp16 subnormal-range terms.
 double err_factor(int kmetric, int DP) {
+  if (kmetric == 7) return 0.0;  // integer sums of code differences: exact
   const double u = std::ldexp(1.0, -24);
   if (kmetric == 4) {
     const double u2 = std::ldexp(1.0, -23);
@@ -503,6 +538,7 @@ const TuneKey kTuneKeys[] = {
     {"xhswz", &Tuning::xhswz, 0, 1, nullptr, "xhswz must be 0 or 1"},
     {"i8", &Tuning::i8, -1, 1, nullptr, "i8 must be -1, 0 or 1"},
     {"i8w", &Tuning::i8w, -1, 1, nullptr, "i8w must be -1, 0 or 1"},
+    {"i8l1", &Tuning::i8l1, -1, 1, nullptr, "i8l1 must be -1, 0 or 1"},
     {"s3gq", &Tuning::s3gq, 0, 0, kSetS3gq, "s3gq must be 0 (auto) or 1, 2, 4, 8, 16, 32"},
     {"ophase", &Tuning::ophase, -1, kRegionMax, nullptr, "ophase must be -1 (auto) .. 64"},
     {"order", &Tuning::order, -1, kRegionMax, nullptr,

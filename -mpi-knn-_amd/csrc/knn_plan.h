@@ -21,6 +21,7 @@ struct Tuning {
   int fp16 = -1;         // fp16 candidate pass: -1 auto, 0 off, 1 on
   int i8 = -1;           // int8 candidate pass: -1 auto, 0 off, 1 on (where the data allow)
   int i8w = -1;          // int8 on 32x32x32 (metric 6): -1 auto (where it pads less), 0 off, 1 on
+  int i8l1 = -1;         // L1 on int8 codes (metric 7): -1 auto, 0 off, 1 on (where the data allow)
   int ties = 1;          // reference tie order: 0 off, 1 vote-affecting ties, 2 all ties
   int m16 = -1;          // bf16x3 on the 16x16x32 MFMA layout: -1 auto, 0 off, 1 on
   int64_t seed = 0;      // seeded thresholds: 0 / -1 off, N sample rows (experiment)

@@ -446,6 +446,20 @@ merge_rerank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, in
       i8x = ps.i8x && dq2 == 0.0 && ps.i8dp <= 256;
       if (lane == 0) s_qq = qq;
     }
+    // L1 on int8 codes (kernel metric 7): the proxy is the exact distance
+    // in units of 2^-s only for a query on the train grid and inside the
+    // code range (its code, rebuilt as prep_i8_queries_kernel builds it, is
+    // then the value itself); any other query's proxies are void
+    bool off_grid = false;
+    if (METRIC == 1 && ps.i8c) {
+      bool off = false;
+      for (int c = lane; c < d; c += 64) {
+        const double y = __builtin_ldexp(qv[c], t.jx) - ps.i8c[c];
+        const double r = __builtin_fmin(__builtin_fmax(__builtin_rint(y), -128.0), 127.0);
+        off = off || !(y == r);
+      }
+      off_grid = __ballot(off) != 0;
+    }
     // proxies are in scaled units (operands 2^jx (x - mu), knn_prep.hip):
     // unscale exactly; operand values outside the format's normal range add
     // absolute error terms (ue per element, up per product, scaled units)
@@ -457,7 +471,7 @@ merge_rerank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, in
     // valid: 1 usable, 0 operands out of the format's range (exact rescan),
     // -1 a non-finite input value (no neighbours are reported)
     const float vq = ps.valid ? ps.valid[q] : 1.0f;
-    const bool void_q = !(vq > 0.0f);
+    const bool void_q = !(vq > 0.0f) || off_grid;
     const bool nonfinite = vq < 0.0f;
     // union in registers; min over full lists of their R-th (worst kept) entry
     // (queries in region order: the query's lists sit at its position)

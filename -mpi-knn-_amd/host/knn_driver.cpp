@@ -13,7 +13,9 @@
 // Extra flags: --gpus N (default 1), --mode query|train (multi-GPU layout),
 // --strict (exit 1 unless N_* divisible by --gpus, as MPI_Abort cpp:127-129),
 // --threads T (CSV parsing threads), --output path, --timings (per-phase
-// seconds on stderr; stdout stays the reference's),
+// seconds on stderr; stdout stays the reference's), --tune KEY=VALUE (a
+// tuning key of the library, knn_set_tuning; repeatable -- e.g. --tune i8l1=1
+// for the Manhattan pass on int8 codes of byte-valued CSVs),
 // --K_list k1,k2,... (needs --Validation true): the validation pass scores
 // every K of the list from one search (knn_group_classify_sweep), prints
 // "K = <k> accuracy = <acc>" per K in list order, selects the first K whose
@@ -35,6 +37,7 @@
 #include <iostream>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "csv.h"
@@ -59,6 +62,7 @@ struct Config {
   bool timings = false;
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
+  std::vector<std::pair<std::string, long long>> tune;  // --tune KEY=VALUE (knn_set_tuning keys)
 };
 
 bool parse_bool(const std::string& v) { return v == "true" || v == "1" || v == "yes"; }
@@ -69,11 +73,13 @@ void usage() {
           "  [--class_cnt C] [--Euclidean_distance true|false] [--Normalize true|false]\n"
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
-          "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo]\n"
+          "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--tune KEY=VALUE]...\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
-          "  (no validation file is read)\n");
+          "  (no validation file is read)\n"
+          "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
+          "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n");
 }
 
 // "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit
@@ -132,6 +138,16 @@ int parse_args(int argc, char** argv, Config& c) {
         return 1;
       }
     }
+    else if (a == "tune") {
+      const size_t e = v.find('=');
+      char* end = nullptr;
+      const long long val = e == std::string::npos ? 0 : strtoll(v.c_str() + e + 1, &end, 10);
+      if (e == std::string::npos || e == 0 || end == v.c_str() + e + 1 || *end) {
+        fprintf(stderr, "--tune takes KEY=VALUE with an integer value\n");
+        return 1;
+      }
+      c.tune.emplace_back(v.substr(0, e), val);
+    }
     else { fprintf(stderr, "unknown flag --%s\n", a.c_str()); usage(); return 1; }
   }
   return 0;
@@ -184,6 +200,8 @@ int main(int argc, char** argv) {
 
   knn_group* g = nullptr;
   if (knn_group_create(&g, c.gpus, nullptr, c.mode)) die(knn_last_error());
+  for (const auto& kv : c.tune)
+    if (knn_group_set_tuning(g, kv.first.c_str(), kv.second)) die(knn_last_error());
 
   using clk = std::chrono::steady_clock;
   const auto start = clk::now();  // ≙ MPI_Barrier + MPI_Wtime, cpp:133-134

@@ -336,6 +336,14 @@ int knn_last_geometry(knn_ctx* ctx, int64_t out[4]);
  * dimension; a query off the train set's grid or beyond the codes' range
  * goes to the exact rescan.  It has no precision mode of its own (tuning
  * keys "i8", "i8w").
+ * L1 (Manhattan) takes the fp32 VALU pass (path 1), except that AUTO runs
+ * batches of >= 4096 queries (k <= 63) against an integer-coded train set at
+ * d <= 256 on the same int8 codes (kernel path 7: v_sad_u8, four dims per
+ * lane per instruction; sums of absolute code differences are the
+ * reference's distances times 2^s, exactly), until a batch leaves > 1/16 of
+ * its queries to the rescan (queries off the train set's grid or beyond the
+ * codes' range go there).  Tuning key "i8l1": 1 at every batch size, 0 never.
+ * d > 256 (MNIST's 784 included) stays on the fp32 stream kernel.
  * Environment override at knn_create: KNN_PRECISION=fp32|bf16x3|fp16. */
 #define KNN_PRECISION_AUTO 0
 #define KNN_PRECISION_FP32 1
@@ -344,7 +352,8 @@ int knn_last_geometry(knn_ctx* ctx, int64_t out[4]);
 int knn_set_precision(knn_ctx* ctx, int mode);
 /* Candidate kernel flavour of the last search: 0 fp32 L2, 1 fp32 L1, 2 bf16x3
  * L2 (32x32x16 MFMA), 3 bf16x3 L2 (16x16x32), 4 fp16 L2 (16x16x32), 5 int8
- * L2 (16x16x64, exact integer dot products), 6 int8 L2 (32x32x32). */
+ * L2 (16x16x64, exact integer dot products), 6 int8 L2 (32x32x32), 7 L1 on
+ * int8 codes (v_sad_u8, exact integer sums; d <= 256). */
 int knn_last_candidate_path(knn_ctx* ctx);
 /* Name of the last candidate kernel launched, as rocprofv3 reports it
  * without namespace, spaces and argument list (e.g. "cand_kernel<128,4,4,8>"). */
@@ -357,7 +366,9 @@ const char* knn_last_kernel_name(knn_ctx* ctx);
  * L2-resident staging, no workgroup barrier -- results invalid; bit 2: no
  * per-query global threshold exchange, results stay exact); -1 = auto for "fp16" (fp16
  * candidate pass: 0 off, 1 on), "i8" (the int8 candidate pass where the
- * train set is integer-coded: 0 off, 1 on at every batch size), "i8w" (int8
+ * train set is integer-coded: 0 off, 1 on at every batch size; L2 only),
+ * "i8l1" (the L1 pass on int8 codes, path 7, where the train set is
+ * integer-coded and d <= 256: 0 off, 1 on at every batch size, -1 auto), "i8w" (int8
  * kernel: -1 auto, 0 the 16x16x64 one, 1 the 32x32x32 one; also read by
  * knn_set_train*, whose norm blocks interleave the rows over that kernel's
  * lane lists -- set it before the train set: a later change keeps results

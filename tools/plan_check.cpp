@@ -28,6 +28,7 @@ int fake_s3q_blocks() { return 1; }
 int fake_qpw(int metric, int) { return metric == 5 ? g_qpw5 : 32; }
 int fake_trows(int metric, int DP) {
   if ((metric == 2 || metric == 4) && DP > 256) return kS3Rows;
+  if (metric == 7) return DP > 128 ? 64 : 128;  // (knn_cand_sad.hip's own tiles)
   return DP <= 256 ? g_trows : 128;
 }
 bool fake_qres(int DP) { return DP % 64 == 0; }
@@ -61,6 +62,7 @@ bool list_len_instantiated(const SearchPlan& p) {
     case 1: return R == 8 || R == 16;
     case 3: case 4: return R == 4;
     case 5: case 6: return R == 4 || R == 8;
+    case 7: return R == 8 || R == 16;
     default: return R == 4 || R == 8 || R == 16;
   }
 }
@@ -96,6 +98,21 @@ void check(const Shape& sh, const Tuning& tune, const char* tkey, int64_t tval) 
   REQUIRE(!p.i8resc || p.kmetric == 6);
   REQUIRE(!p.query_order || (in.ord_P > 0 && p.kmetric >= 4 && !p.s3));
   REQUIRE(p.cap >= 1 && p.cap <= sh.m);
+  // path 7 (L1 on int8 codes): only for L1 on an integer-coded set at d <=
+  // 256 and never with the key at 0; "i8" alone does not reach it; the plain
+  // int8 image at pad_dim_i8w, the fp32 L1 kernel's list layout, no L2 device
+  if (p.kmetric == 7) {
+    REQUIRE(sh.metric == KNN_METRIC_L1 && sh.i8_ok && sh.d <= 256 && tune.i8l1 != 0);
+    REQUIRE(tune.i8l1 == 1 || (sh.precision == KNN_PRECISION_AUTO && sh.m >= 4096 && sh.W <= 64));
+    REQUIRE(p.image == IMG_I8 && p.DP == pad_dim_i8w(sh.d) && p.i8_swz == 0 && p.xsw == 0);
+    REQUIRE(p.lps == 2 && (p.nw == 4 || p.nw == 8) && p.qpw == 32 && !p.s3);
+    REQUIRE(!p.i8resc && !p.query_order && p.seed_rows == 0);
+    REQUIRE(err_factor(7, p.DP) == 0.0);
+    REQUIRE(p.auto_arm == (tune.i8l1 < 0 && !p.abl));
+  } else if (sh.metric == KNN_METRIC_L1) {
+    REQUIRE(p.kmetric == 1);
+    REQUIRE(tune.i8l1 != 1 || !sh.i8_ok || sh.d > 256);
+  }
 #undef REQUIRE
 }
 
@@ -141,7 +158,8 @@ int main() {
       {"ablate", 0, {4, 32}, {}},         {"S", 0, {0, 1, 64}, {-1, 65}},
       {"qres", -1, {-1, 0, 1}, {-2, 2}},   {"s3q", -1, {-1, 0, 1}, {-2, 2}},
       {"xhswz", 1, {0, 1}, {-1, 2}},      {"i8", -1, {-1, 0, 1}, {-2, 2}},
-      {"i8w", -1, {-1, 0, 1}, {-2, 2}},    {"seed", 0, {-1, 0, 8192, 1ll << 40}, {-2}},
+      {"i8w", -1, {-1, 0, 1}, {-2, 2}},    {"i8l1", -1, {-1, 0, 1}, {-2, 2}},
+      {"seed", 0, {-1, 0, 8192, 1ll << 40}, {-2}},
       {"s3gq", 0, {0, 1, 2, 4, 8, 16, 32}, {-1, 3, 64}},
       {"ophase", -1, {-1, 0, 64}, {-2, 65}}, {"order", -1, {-1, 0, 1, 2, 64}, {-2, 65}},
       {"qblk", 0, {0, 1, 1 << 20}, {-1, (1 << 20) + 1}},
