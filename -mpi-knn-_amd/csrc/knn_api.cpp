@@ -142,7 +142,8 @@ int knn_destroy(knn_ctx* ctx) {
 // centre c_i is the middle of dimension i's code range.  Sets ctx->i8_ok.
 static int detect_i8(knn_ctx* ctx, const double* dX, int64_t n, int d) {
   ctx->i8_ok = false;
-  if (pad_dim_i8(d) <= 0) return KNN_OK;
+  // (d <= 256: the int8 passes; up to 1024: the wide L1 pass, "i8l1" = 2)
+  if (pad_dim_i8(d) <= 0 && pad_dim_i8l1w(d) <= 0) return KNN_OK;
   int rc;
   if ((rc = ctx->i8_gs.ensure((size_t)(col_mean_blocks(n) * 2 + 2) * d * sizeof(double) + 16)))
     return rc;
@@ -321,6 +322,7 @@ static int build_train(knn_ctx* ctx, const double* dX, const int32_t* dlab, int6
   ctx->DPh = 0;
   ctx->DPs = 0;
   ctx->DPi = 0;
+  ctx->DPiw = 0;
   ctx->smp_kind = 0;  // the seeding sample is rebuilt for the new train set
   ctx->i8_off = false;
   ctx->fp16_off = false;
@@ -413,6 +415,24 @@ static int ensure_i8(knn_ctx* ctx, int kmetric, hipStream_t s) {
   ctx->i8_x2max = std::ldexp((double)cm, -2 * ctx->i8_s);
   ctx->DPi = DPi;
   ctx->i8_swz = swz;
+  return KNN_OK;
+}
+
+// The image of kernel metric 7 at 256 < d <= 1024 (knn_cand_sad_wide.hip):
+// plain rows of DP code bytes in its own buffer, built on the first wide L1
+// call; the d <= 256 images are untouched.
+static int ensure_i8_wide(knn_ctx* ctx, hipStream_t s) {
+  const TrainDev& t = ctx->train;
+  const int DPw = pad_dim_i8l1w(t.d);
+  if (!ctx->i8_ok || DPw <= 0)
+    return knn_fail(KNN_ERR_ARG, "train set not integer-coded (wide L1 pass on int8 codes)");
+  if (ctx->DPiw == DPw) return KNN_OK;
+  int rc;
+  if ((rc = ctx->XIW.ensure((size_t)t.n_pad * DPw + 1024))) return rc;
+  launch_prep_i8_rows(t.X64, (const double*)ctx->i8_cent.p, t.n, t.d, DPw, t.n_pad, ctx->i8_s,
+                      (signed char*)ctx->XIW.p, s, t.perm);
+  HIP_TRY(hipGetLastError());
+  ctx->DPiw = DPw;
   return KNN_OK;
 }
 
@@ -623,6 +643,7 @@ static const KernelFacts kFacts = {cand_blocks_per_cu, s3q_blocks_per_cu, cand_q
 static int ensure_image(knn_ctx* ctx, const SearchPlan& p, hipStream_t s) {
   switch (p.image) {
     case IMG_I8: return ensure_i8(ctx, p.kmetric, s);
+    case IMG_I8W: return ensure_i8_wide(ctx, s);
     case IMG_FP16: return ensure_fp16(ctx, s);
     case IMG_FP16_S3: return ensure_fp16_s3(ctx, s);
     case IMG_BF16X3: return ensure_bf16x3(ctx, s);
@@ -645,7 +666,7 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   const int kmetric = p.kmetric, DP = p.DP, R = p.R, S = p.S, NL = p.NL, C = p.C, n_qt = p.n_qt;
   const int64_t m_pad = p.m_pad;
   const float* const images[] = {t.X32, (const float*)ctx->XB.p, (const float*)ctx->XH.p, nullptr,
-                                 (const float*)ctx->XI.p};
+                                 (const float*)ctx->XI.p, (const float*)ctx->XIW.p};
   // workspace, sized from the plan
   if ((rc = ctx->Q32.ensure((size_t)m_pad * DP * sizeof(float)))) return rc;
   if ((rc = ctx->qvalid.ensure((size_t)m_pad * sizeof(float)))) return rc;
@@ -720,7 +741,8 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
     launch_prep_i8_queries(dQ, t.mu, qscale, t.jx, DBL_MAX, (const double*)ctx->i8_cent.p, m, t.d,
                            DP, m_pad, ctx->i8_s, (signed char*)ctx->Q32.p, qvalid, s, qperm,
                            p.gthr_init ? (uint32_t*)ctx->gthr.p : nullptr, p.active,
-                           (int*)ctx->ord_bcnt.p, bcnt_clear, (int*)ctx->rescan_cnt.p);
+                           (int*)ctx->ord_bcnt.p, bcnt_clear, (int*)ctx->rescan_cnt.p,
+                           p.image == IMG_I8W);
     if (bcnt_clear) ctx->ord_bcnt_zero = bcnt_clear;
   } else if (p.s3h)
     launch_prep_half_tiled(dQ, t.mu, m, t.d, DP, m_pad, t.jx, -2.0, (unsigned short*)ctx->Q32.p,

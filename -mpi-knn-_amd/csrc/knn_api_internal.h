@@ -81,6 +81,10 @@ struct knn_ctx {
   // int8 image: codes [n_pad][DP + 16 B]; per-dim centres [code units d |
   // value units d] (the latter the merge's mu for this pass); grid stats scratch
   DevBuf XI, i8_cent, i8_gs;
+  // the wide L1-on-codes pass's own image (256 < d <= 1024): plain rows of
+  // DPiw code bytes, n_pad rows (0 = not built)
+  DevBuf XIW;
+  int DPiw = 0;
   DevBuf smp_x64, smp_xl2, smp_img, smp_scr, smp_v, smp_i;
   // region order: centroids [P][d], chain ranks, region starts, image
   // position <-> train row maps; k-means / sort scratch; per-call query order
@@ -104,7 +108,7 @@ struct knn_ctx {
   // normalisation: per-thread partial max/min, bounds, host-API staging
   DevBuf nrm_part, nrm_mm, nrm_X;
   std::vector<DevBuf*> all_bufs() {
-    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &i8_cent, &i8_gs,
+    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &i8_cent, &i8_gs,
             &XH,      &XT16,    &XS16,  &mu,      &mu_part, &Q64, &Q32,    &qvalid, &cand_v,   &cand_i,
             &gthr,    &rescan_q, &rescan_tau, &rescan_cnt, &fr_cnt, &fr_buf, &fr_q, &fr_thr,
             &slow_q,  &totals,  &lk, &mrg, &tie_q, &tie_ws, &o_lab, &o_idx, &o_dist, &o_flags, &nrm_part, &nrm_mm, &nrm_X,

@@ -26,6 +26,9 @@ int pad_dim_fp16_s3(int d);         // padded dim of the fp16 S3 image (multiple
 bool cand_supported(int DP);
 int pad_dim_i8(int d);  // padded dim of the int8 kernel (a multiple of 64, <= 256), -1 if none
 int pad_dim_i8w(int d); // padded dim of the int8 32x32x32 kernel (metric 6), -1 if none
+// padded dim of the wide L1-on-codes image (knn_cand_sad_wide.hip): d in (256, 1024]
+// rounded up to the kernel's 16-dim granule, -1 outside
+int pad_dim_i8l1w(int d);
 
 #define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
 

@@ -168,6 +168,13 @@ bool launch_cand(const CandLaunch& c, hipStream_t s);
 bool launch_cand_sad(const CandLaunch& c, hipStream_t s);
 int sad_blocks_per_cu(int DP, int R, int nw);
 int sad_tile_rows(int DP);
+// kernel metric 7 at 256 < DP <= 1024 (knn_cand_sad_wide.hip): X32 = the plain
+// code rows of launch_prep_i8_rows, Q32 = the step-major query codes of
+// launch_prep_i8_queries' wide form
+bool sad_wide_dp(int DP);
+bool launch_cand_sad_wide(const CandLaunch& c, hipStream_t s);
+int sad_wide_blocks_per_cu(int R, int nw);
+int sad_wide_tile_rows();
 // gthr: the candidate kernel's per-query global thresholds ([m_pad][kGthrSlots] keys)
 // or null when the kernel kept none
 // failed queries are appended to rescan_q with rescan_tau = the W-th exact
@@ -333,7 +340,15 @@ void launch_prep_i8_queries(const double* Q64, const double* mu, double scale, i
                             double limit, const double* cent, int64_t m, int d, int DP,
                             int64_t m_pad, int s, signed char* out, float* valid, hipStream_t st,
                             const int* qperm, uint32_t* gthr, int active, int* zero = nullptr,
-                            int64_t nzero = 0, int* zero4 = nullptr);
+                            int64_t nzero = 0, int* zero4 = nullptr, bool wide = false);
+// wide (kernel metric 7 at DP > 256, knn_cand_sad_wide.hip): the same codes
+// and validity test, the code rows step-major -- the 16 codes of step c of
+// query j of 32-query group g at byte ((g DP / 16 + c) 32 + j) 16.
+// The train side of that pass: plain rows of DP code bytes (zero codes in the
+// pad dims and on pad rows), n_pad rows, no seeds
+void launch_prep_i8_rows(const double* X64, const double* cent, int64_t n, int d, int DP,
+                         int64_t n_pad, int s, signed char* out, hipStream_t st,
+                         const int* perm = nullptr);
 // The reference's exact neighbour order on exact distance ties (knn_select.hip,
 // "reference tie order"): libstdc++ std::sort (introsort) emulated over all
 // n exact distances of each listed query, restricted to the ranges that

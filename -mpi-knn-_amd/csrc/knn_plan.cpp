@@ -52,6 +52,13 @@ int pad_dim_i8w(int d) {
   return -1;
 }
 
+// L1 on int8 codes above 256 dims (knn_cand_sad_wide.hip): one ds_read_b128
+// of a row is 16 codes, the kernel's step, so any multiple of 16 up to 1024
+// (255 * 1024 < 2^24: the sums stay exact floats); d = 784 pads nothing
+int pad_dim_i8l1w(int d) {
+  return d > 256 && d <= 1024 ? (d + 15) / 16 * 16 : -1;
+}
+
 // fp16 S3 kernel above 256 dims: any multiple of 32
 int pad_dim_fp16_s3(int d) {
   const int DP = (d + 31) / 32 * 32;
@@ -195,7 +202,13 @@ static bool use_i8(const PlanIn& in) {
 // run-to-run spread at both measured shapes: 1M x 10k, d = 128: 88.47-88.71
 // -> 11.80-11.83 ms; 40000 x 4096: 1.677-1.688 -> 0.415-0.432 ms
 // (profiles/ab_log.md, "l1sad").  "i8" (the L2 pass) does not reach it.
+// Value 2: as 1, and at 256 < d <= 1024 the wide form of the pass
+// (knn_cand_sad_wide.hip, query codes re-read per tile).  Opt-in only: AUTO
+// and 1 leave those widths on the fp32 stream kernel.
 constexpr bool kI8L1Auto = true;
+static bool use_i8l1_wide(const PlanIn& in) {
+  return in.metric == KNN_METRIC_L1 && in.i8_ok && in.tune.i8l1 == 2 && pad_dim_i8l1w(in.d) > 0;
+}
 static bool use_i8l1(const PlanIn& in) {
   if (in.metric != KNN_METRIC_L1 || !in.i8_ok || pad_dim_i8w(in.d) <= 0) return false;
   if (in.tune.i8l1 >= 0) return in.tune.i8l1 > 0;
@@ -213,8 +226,11 @@ static bool use_bf16x3(const PlanIn& in) {
 // (knn_cand_res.hip, res_variant, which refuses the launch of any other): a
 // variant build that instantiates more extends this with it.
 static bool resident_variant(int DP, int R, int M, int NW) {
-  // metric 7 (knn_cand_sad.hip): DP of pad_dim_i8w, R in {8, 16}, 4 or 8 waves
-  if (M == 7) return pad_dim_i8w(DP) == DP && (R == 8 || R == 16) && (NW == 4 || NW == 8);
+  // metric 7 (knn_cand_sad.hip): DP of pad_dim_i8w, R in {8, 16}, 4 or 8 waves;
+  // its wide form (knn_cand_sad_wide.hip) takes DP at run time
+  if (M == 7)
+    return (pad_dim_i8w(DP) == DP || pad_dim_i8l1w(DP) == DP) && (R == 8 || R == 16) &&
+           (NW == 4 || NW == 8);
   return (M != 2 || DP % 16 == 0) && (M != 1 || (NW == 4 && R != 4)) &&
          (M < 3 || (DP % 32 == 0 && (R == 4 || (M >= 5 && R == 8)) && (NW == 8 || M >= 4))) &&
          (NW != 16 || M == 4) && (M != 5 || (DP % 64 == 0 && (NW == 8 || NW == 4))) &&
@@ -339,6 +355,12 @@ SearchPlan plan_search(const PlanIn& in) {
     p.kmetric = 7;
     p.image = IMG_I8;
     p.DP = pad_dim_i8w(in.d);
+  } else if (use_i8l1_wide(in)) {
+    // the same pass on plain rows of DP code bytes (train order: no region
+    // order and no norm blocks above 256 dims)
+    p.kmetric = 7;
+    p.image = IMG_I8W;
+    p.DP = pad_dim_i8l1w(in.d);
   } else if (use_i8(in)) {
     p.kmetric = i8_kernel_d(tune, in.d);
     p.image = IMG_I8;
@@ -377,8 +399,11 @@ SearchPlan plan_search(const PlanIn& in) {
   else p.nw = 4;
   // queries per wave of the resident kernel (int8: 16 x the build's query
   // blocks); the int8 kernel with 64 queries per wave also runs 4 waves
-  p.qpw = !p.s3 && DP <= 256 ? in.facts.cand_queries_per_wave(kmetric, DP) : 32;
-  p.qpb = p.s3 ? kS3Rows : (DP <= 256 ? p.qpw * p.nw : kQPB);
+  // (metric 7 at DP > 256 is a resident-style kernel too: its own facts, not
+  // the stream kernel's 128 queries)
+  const bool res = !p.s3 && (DP <= 256 || kmetric == 7);
+  p.qpw = res ? in.facts.cand_queries_per_wave(kmetric, DP) : 32;
+  p.qpb = p.s3 ? kS3Rows : (res ? p.qpw * p.nw : kQPB);
   p.n_qt = (int)((m + p.qpb - 1) / p.qpb);
   p.m_pad = (int64_t)p.n_qt * p.qpb;
   p.n_pad3 = (in.n + kS3Rows - 1) / kS3Rows * kS3Rows;
@@ -426,7 +451,7 @@ SearchPlan plan_search(const PlanIn& in) {
   if (p.gk > (p.s3 ? 16 : 4)) p.gk = 0;
   if (tune.gk >= 0) p.gk = std::min(tune.gk, p.s3 ? 16 : 4);
   p.ablate = tune.ablate;
-  p.use_gthr = (p.s3 ? p.s3q && p.gk > 0 : DP <= 256) && !(tune.ablate & 4);
+  p.use_gthr = (p.s3 ? p.s3q && p.gk > 0 : res) && !(tune.ablate & 4);
   // gthr init (slots of groups without a split stay 0, never the max); the
   // int8 query builder writes it with the operands (ablate bit 5, an
   // experiment: keep the previous call's final thresholds -- valid only for
@@ -471,7 +496,10 @@ SearchPlan plan_search(const PlanIn& in) {
     snprintf(p.kernel, sizeof p.kernel, "cand_s3_kernel<%d,%s,%s>", p.R, p.s3h ? "true" : "false",
              p.s3q ? "true" : "false");
   else if (kmetric == 7) {
-    snprintf(p.kernel, sizeof p.kernel, "cand_sad_kernel<%d,%d,%d>", DP, p.R, p.nw);
+    if (DP > 256)
+      snprintf(p.kernel, sizeof p.kernel, "cand_sad_wide_kernel<%d,%d>", p.R, p.nw);
+    else
+      snprintf(p.kernel, sizeof p.kernel, "cand_sad_kernel<%d,%d,%d>", DP, p.R, p.nw);
     p.ok = resident_variant(DP, p.R, kmetric, p.nw);
   } else if (DP <= 256) {
     snprintf(p.kernel, sizeof p.kernel, "cand_kernel<%d,%d,%d,%d>", DP, p.R, kmetric, p.nw);
@@ -538,7 +566,7 @@ const TuneKey kTuneKeys[] = {
     {"xhswz", &Tuning::xhswz, 0, 1, nullptr, "xhswz must be 0 or 1"},
     {"i8", &Tuning::i8, -1, 1, nullptr, "i8 must be -1, 0 or 1"},
     {"i8w", &Tuning::i8w, -1, 1, nullptr, "i8w must be -1, 0 or 1"},
-    {"i8l1", &Tuning::i8l1, -1, 1, nullptr, "i8l1 must be -1, 0 or 1"},
+    {"i8l1", &Tuning::i8l1, -1, 2, nullptr, "i8l1 must be -1, 0, 1 or 2 (2: also at 256 < d <= 1024)"},
     {"s3gq", &Tuning::s3gq, 0, 0, kSetS3gq, "s3gq must be 0 (auto) or 1, 2, 4, 8, 16, 32"},
     {"ophase", &Tuning::ophase, -1, kRegionMax, nullptr, "ophase must be -1 (auto) .. 64"},
     {"order", &Tuning::order, -1, kRegionMax, nullptr,

@@ -21,7 +21,9 @@ struct Tuning {
   int fp16 = -1;         // fp16 candidate pass: -1 auto, 0 off, 1 on
   int i8 = -1;           // int8 candidate pass: -1 auto, 0 off, 1 on (where the data allow)
   int i8w = -1;          // int8 on 32x32x32 (metric 6): -1 auto (where it pads less), 0 off, 1 on
-  int i8l1 = -1;         // L1 on int8 codes (metric 7): -1 auto, 0 off, 1 on (where the data allow)
+  // L1 on int8 codes (metric 7): -1 auto, 0 off, 1 on (where the data allow),
+  // 2 as 1 and also at 256 < d <= 1024 (knn_cand_sad_wide.hip)
+  int i8l1 = -1;
   int ties = 1;          // reference tie order: 0 off, 1 vote-affecting ties, 2 all ties
   int m16 = -1;          // bf16x3 on the 16x16x32 MFMA layout: -1 auto, 0 off, 1 on
   int64_t seed = 0;      // seeded thresholds: 0 / -1 off, N sample rows (experiment)
@@ -73,7 +75,8 @@ struct PlanIn {
 };
 
 // the train image the candidate kernel reads (knn_api.cpp: ensure_*)
-enum TrainImage { IMG_FP32, IMG_BF16X3, IMG_FP16, IMG_FP16_S3, IMG_I8 };
+// (IMG_I8W: the plain int8 rows of the wide L1-on-codes pass, d > 256)
+enum TrainImage { IMG_FP32, IMG_BF16X3, IMG_FP16, IMG_FP16_S3, IMG_I8, IMG_I8W };
 
 struct SearchPlan {
   bool ok;           // false: no kernel is instantiated for this geometry

@@ -514,6 +514,8 @@ void launch_prep_i8_train(const double* X64, const double* cent, int64_t n, int 
 // (which ran before) and cleared here for the next call's histogram; zero4:
 // the call's rescan / tie counters (4 ints, read by the merge), cleared here
 // instead of by a memset launch after the candidate kernel.
+// WIDE: the step-major code rows of knn_cand_sad_wide.hip (knn_kernels.h).
+template <bool WIDE>
 __global__ void __launch_bounds__(256)
 prep_i8_queries_kernel(const double* __restrict__ Q64, const double* __restrict__ mu, double scale,
                        int jx, double limit, const double* __restrict__ cent, int64_t m, int d,
@@ -546,7 +548,10 @@ prep_i8_queries_kernel(const double* __restrict__ Q64, const double* __restrict_
         const double y = __builtin_ldexp(Q64[q * d + c], s) - cent[c];
         k = (int)__builtin_fmin(__builtin_fmax(__builtin_rint(y), -128.0), 127.0);
       }
-      out[row * DP + c] = (signed char)k;
+      if (WIDE)
+        out[(((row >> 5) * (DP >> 4) + (c >> 4)) * 32 + (row & 31)) * 16 + (c & 15)] = (signed char)k;
+      else
+        out[row * DP + c] = (signed char)k;
     }
     if (gthr && lane < kGthrSlots) gthr[row * kGthrSlots + lane] = lane < active ? kGthrInit : 0u;
   }
@@ -556,12 +561,44 @@ void launch_prep_i8_queries(const double* Q64, const double* mu, double scale, i
                             double limit, const double* cent, int64_t m, int d, int DP,
                             int64_t m_pad, int s, signed char* out, float* valid, hipStream_t st,
                             const int* qperm, uint32_t* gthr, int active, int* zero,
-                            int64_t nzero, int* zero4) {
+                            int64_t nzero, int* zero4, bool wide) {
   int64_t blocks = (m_pad + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(prep_i8_queries_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q64, mu,
-                     scale, jx, limit, cent, m, d, DP, m_pad, s, out, valid, qperm, gthr, active,
-                     zero, nzero, zero4);
+  if (wide)
+    hipLaunchKernelGGL(prep_i8_queries_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, Q64,
+                       mu, scale, jx, limit, cent, m, d, DP, m_pad, s, out, valid, qperm, gthr,
+                       active, zero, nzero, zero4);
+  else
+    hipLaunchKernelGGL(prep_i8_queries_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, Q64,
+                       mu, scale, jx, limit, cent, m, d, DP, m_pad, s, out, valid, qperm, gthr,
+                       active, zero, nzero, zero4);
+}
+
+// The wide L1-on-codes pass's train rows (knn_cand_sad_wide.hip): DP code
+// bytes per row, codes k = x 2^s - c_i as prep_i8_train_kernel's, zero in the
+// pad dims and on pad rows; one wave per row.
+__global__ void __launch_bounds__(256)
+prep_i8_rows_kernel(const double* __restrict__ X64, const double* __restrict__ cent, int64_t n,
+                    int d, int DP, int64_t n_pad, int s, signed char* __restrict__ out,
+                    const int* __restrict__ perm) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_pad; row += wstride) {
+    const int64_t src = src_row(perm, row, n);
+    for (int c = lane; c < DP; c += 64) {
+      int k = 0;
+      if (row < n && c < d) k = (int)__builtin_rint(__builtin_ldexp(X64[src * d + c], s) - cent[c]);
+      out[row * DP + c] = (signed char)k;
+    }
+  }
+}
+
+void launch_prep_i8_rows(const double* X64, const double* cent, int64_t n, int d, int DP,
+                         int64_t n_pad, int s, signed char* out, hipStream_t st, const int* perm) {
+  int64_t blocks = (n_pad + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(prep_i8_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X64, cent, n, d,
+                     DP, n_pad, s, out, perm);
 }
 
 __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {

@@ -79,7 +79,8 @@ void usage() {
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
           "  (no validation file is read)\n"
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
-          "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n");
+          "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
+          "  (i8l1=2: also at 256 < dim <= 1024)\n");
 }
 
 // "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit

@@ -433,7 +433,8 @@ class Classifier:
         automatic.  "i8l1": L1 searches on the int8 codes of an
         integer-coded train set at d <= 256 (candidate path 7, v_sad_u8; results
         unchanged): 1 at every batch size, 0 never, -1 auto (batches of >= 4096
-        queries in PRECISION_AUTO).  "order" and "nblk" shape the train layout and are read by
+        queries in PRECISION_AUTO), 2 as 1 and also at 256 < d <= 1024 (the
+        wide kernel, cand_sad_wide_kernel; opt-in only).  "order" and "nblk" shape the train layout and are read by
         set_train: "order" -1 = region order only for integer-coded sets whose
         int8 image is <= 192 MB (n / 16384 regions, up to 64, at least 8),
         1 = n / 16384 regions (off below n = 32768); "nblk" -1 = norm blocks

@@ -343,7 +343,9 @@ int knn_last_geometry(knn_ctx* ctx, int64_t out[4]);
  * reference's distances times 2^s, exactly), until a batch leaves > 1/16 of
  * its queries to the rescan (queries off the train set's grid or beyond the
  * codes' range go there).  Tuning key "i8l1": 1 at every batch size, 0 never.
- * d > 256 (MNIST's 784 included) stays on the fp32 stream kernel.
+ * d > 256 (MNIST's 784 included) stays on the fp32 stream kernel unless
+ * "i8l1" = 2 asks for the wide form of the pass, which serves 256 < d <= 1024
+ * (opt-in: never AUTO's choice).
  * Environment override at knn_create: KNN_PRECISION=fp32|bf16x3|fp16. */
 #define KNN_PRECISION_AUTO 0
 #define KNN_PRECISION_FP32 1
@@ -368,7 +370,9 @@ const char* knn_last_kernel_name(knn_ctx* ctx);
  * candidate pass: 0 off, 1 on), "i8" (the int8 candidate pass where the
  * train set is integer-coded: 0 off, 1 on at every batch size; L2 only),
  * "i8l1" (the L1 pass on int8 codes, path 7, where the train set is
- * integer-coded and d <= 256: 0 off, 1 on at every batch size, -1 auto), "i8w" (int8
+ * integer-coded and d <= 256: 0 off, 1 on at every batch size, -1 auto; 2: as
+ * 1, and also at 256 < d <= 1024 on the wide kernel, cand_sad_wide_kernel --
+ * beyond 1024 dims, off the grid or under L2 it plans what 0 plans), "i8w" (int8
  * kernel: -1 auto, 0 the 16x16x64 one, 1 the 32x32x32 one; also read by
  * knn_set_train*, whose norm blocks interleave the rows over that kernel's
  * lane lists -- set it before the train set: a later change keeps results

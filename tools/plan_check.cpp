@@ -28,7 +28,8 @@ int fake_s3q_blocks() { return 1; }
 int fake_qpw(int metric, int) { return metric == 5 ? g_qpw5 : 32; }
 int fake_trows(int metric, int DP) {
   if ((metric == 2 || metric == 4) && DP > 256) return kS3Rows;
-  if (metric == 7) return DP > 128 ? 64 : 128;  // (knn_cand_sad.hip's own tiles)
+  // (knn_cand_sad.hip's own tiles; knn_cand_sad_wide.hip's above 256 dims)
+  if (metric == 7) return DP > 128 ? 64 : 128;
   return DP <= 256 ? g_trows : 128;
 }
 bool fake_qres(int DP) { return DP % 64 == 0; }
@@ -57,7 +58,7 @@ void fail(const Shape& sh, const char* tkey, int64_t tval, const SearchPlan& p, 
 bool list_len_instantiated(const SearchPlan& p) {
   const int R = p.R;
   if (p.qres || p.s3q) return R == 8;
-  if (p.s3 || p.DP > 256) return R == 8 || R == 16;
+  if (p.s3 || (p.DP > 256 && p.kmetric != 7)) return R == 8 || R == 16;
   switch (p.kmetric) {
     case 1: return R == 8 || R == 16;
     case 3: case 4: return R == 4;
@@ -83,7 +84,7 @@ void check(const Shape& sh, const Tuning& tune, const char* tkey, int64_t tval) 
   REQUIRE(p.NL == p.lps * p.S);
   REQUIRE(p.C >= 1 && p.C <= p.NL * p.R && p.C <= kMaxUnion);
   REQUIRE(p.m_pad == (int64_t)p.n_qt * p.qpb && p.m_pad >= sh.m && p.m_pad - sh.m < p.qpb);
-  if (!p.s3 && p.DP <= 256) REQUIRE(p.qpb == p.qpw * p.nw);
+  if (!p.s3 && (p.DP <= 256 || p.kmetric == 7)) REQUIRE(p.qpb == p.qpw * p.nw);
   REQUIRE(p.gk >= 0 && p.gk <= (p.s3 ? 16 : 4));
   REQUIRE(p.G == 4 || p.G == 8);
   REQUIRE(p.gmask == (p.gk ? p.G - 1 : 3));
@@ -91,33 +92,50 @@ void check(const Shape& sh, const Tuning& tune, const char* tkey, int64_t tval) 
   REQUIRE(list_len_instantiated(p));
   REQUIRE(!p.qres || p.s3q);
   REQUIRE(!p.s3q || p.s3h);
-  REQUIRE(!p.use_gthr || (!p.s3 && p.DP <= 256) || p.s3q);
+  REQUIRE(!p.use_gthr || (!p.s3 && (p.DP <= 256 || p.kmetric == 7)) || p.s3q);
   REQUIRE(!p.gthr_init || p.use_gthr);
   REQUIRE(p.n_tiles >= 1 && p.n_tiles * p.trows == (p.s3 ? p.n_pad3 : n_pad));
   REQUIRE(p.qblk >= 0 && p.qblk <= p.n_qt);
   REQUIRE(!p.i8resc || p.kmetric == 6);
   REQUIRE(!p.query_order || (in.ord_P > 0 && p.kmetric >= 4 && !p.s3));
   REQUIRE(p.cap >= 1 && p.cap <= sh.m);
-  // path 7 (L1 on int8 codes): only for L1 on an integer-coded set at d <=
-  // 256 and never with the key at 0; "i8" alone does not reach it; the plain
-  // int8 image at pad_dim_i8w, the fp32 L1 kernel's list layout, no L2 device
+  // path 7 (L1 on int8 codes): only for L1 on an integer-coded set and never
+  // with the key at 0; "i8" alone does not reach it.  At d <= 256: the key at
+  // 1 or 2, or AUTO's rule; the plain int8 image at pad_dim_i8w.  At 256 < d
+  // <= 1024: the key at 2 only (never AUTO's choice, so it arms no AUTO
+  // decision); plain rows at pad_dim_i8l1w, the wide kernel, its own query
+  // tile and tile rows.  Either way the fp32 L1 kernel's list layout, one
+  // list per lane, R 8 or 16, no query order, no int8 rescan filter.
   if (p.kmetric == 7) {
-    REQUIRE(sh.metric == KNN_METRIC_L1 && sh.i8_ok && sh.d <= 256 && tune.i8l1 != 0);
-    REQUIRE(tune.i8l1 == 1 || (sh.precision == KNN_PRECISION_AUTO && sh.m >= 4096 && sh.W <= 64));
-    REQUIRE(p.image == IMG_I8 && p.DP == pad_dim_i8w(sh.d) && p.i8_swz == 0 && p.xsw == 0);
+    REQUIRE(sh.metric == KNN_METRIC_L1 && sh.i8_ok && sh.d <= 1024 && tune.i8l1 != 0);
+    if (sh.d <= 256) {
+      REQUIRE(tune.i8l1 >= 1 || (sh.precision == KNN_PRECISION_AUTO && sh.m >= 4096 && sh.W <= 64));
+      REQUIRE(p.image == IMG_I8 && p.DP == pad_dim_i8w(sh.d));
+      REQUIRE(!strncmp(p.kernel, "cand_sad_kernel<", 16));
+    } else {
+      REQUIRE(tune.i8l1 == 2);
+      REQUIRE(p.image == IMG_I8W && p.DP == pad_dim_i8l1w(sh.d) && p.DP > 256 && p.DP % 16 == 0);
+      REQUIRE(p.DP >= sh.d && p.DP - sh.d < 16);
+      REQUIRE(!strncmp(p.kernel, "cand_sad_wide_kernel<", 21));
+      REQUIRE(p.trows == fake_trows(7, p.DP) && p.qpb == 32 * p.nw);
+    }
+    REQUIRE(p.i8_swz == 0 && p.xsw == 0);
     REQUIRE(p.lps == 2 && (p.nw == 4 || p.nw == 8) && p.qpw == 32 && !p.s3);
+    REQUIRE(p.R == 8 || p.R == 16);
     REQUIRE(!p.i8resc && !p.query_order && p.seed_rows == 0);
     REQUIRE(err_factor(7, p.DP) == 0.0);
     REQUIRE(p.auto_arm == (tune.i8l1 < 0 && !p.abl));
   } else if (sh.metric == KNN_METRIC_L1) {
     REQUIRE(p.kmetric == 1);
-    REQUIRE(tune.i8l1 != 1 || !sh.i8_ok || sh.d > 256);
+    REQUIRE(tune.i8l1 < 1 || !sh.i8_ok || sh.d > 256);
+    REQUIRE(tune.i8l1 != 2 || !sh.i8_ok || sh.d > 1024);
   }
+  REQUIRE((pad_dim_i8l1w(sh.d) > 0) == (sh.d > 256 && sh.d <= 1024));
 #undef REQUIRE
 }
 
 void walk(const Tuning& tune, const char* tkey, int64_t tval) {
-  static const int ds[] = {1, 16, 24, 96, 128, 256, 257, 288, 320, 960};
+  static const int ds[] = {1, 16, 24, 96, 128, 256, 257, 288, 300, 320, 784, 960, 1024, 1025};
   static const int64_t ns[] = {1, 255, 2000, 40000, 1000000, 12500000};
   static const int64_t ms[] = {1, 127, 4095, 4096, 10000, 131072, 1000000};
   // the path's cap: k <= 1000 on this path, W = k + 1 (and never above n)
@@ -158,7 +176,7 @@ int main() {
       {"ablate", 0, {4, 32}, {}},         {"S", 0, {0, 1, 64}, {-1, 65}},
       {"qres", -1, {-1, 0, 1}, {-2, 2}},   {"s3q", -1, {-1, 0, 1}, {-2, 2}},
       {"xhswz", 1, {0, 1}, {-1, 2}},      {"i8", -1, {-1, 0, 1}, {-2, 2}},
-      {"i8w", -1, {-1, 0, 1}, {-2, 2}},    {"i8l1", -1, {-1, 0, 1}, {-2, 2}},
+      {"i8w", -1, {-1, 0, 1}, {-2, 2}},    {"i8l1", -1, {-1, 0, 1, 2}, {-2, 3}},
       {"seed", 0, {-1, 0, 8192, 1ll << 40}, {-2}},
       {"s3gq", 0, {0, 1, 2, 4, 8, 16, 32}, {-1, 3, 64}},
       {"ophase", -1, {-1, 0, 64}, {-2, 65}}, {"order", -1, {-1, 0, 1, 2, 64}, {-2, 65}},
