@@ -323,6 +323,7 @@ static int build_train(knn_ctx* ctx, const double* dX, const int32_t* dlab, int6
   ctx->DPs = 0;
   ctx->DPi = 0;
   ctx->DPiw = 0;
+  ctx->DPu = 0;
   ctx->smp_kind = 0;  // the seeding sample is rebuilt for the new train set
   ctx->i8_off = false;
   ctx->fp16_off = false;
@@ -433,6 +434,33 @@ static int ensure_i8_wide(knn_ctx* ctx, hipStream_t s) {
                       (signed char*)ctx->XIW.p, s, t.perm);
   HIP_TRY(hipGetLastError());
   ctx->DPiw = DPw;
+  return KNN_OK;
+}
+
+// The image of kernel metric 8 (knn_cand_fix16.hip): rows of DP 16-bit
+// fixed-point codes of 2^e (x - mu), e = jx + 5 -- max |x - mu| 2^jx < 2^9
+// (build_train), so the train codes stay within 32768 +- 2^14, half the range,
+// and jx's own cap keeps e defined for a constant train set -- in its own
+// buffer, built on the first such call; with it the largest coding error of
+// a row (u16_dx, code units), which the merge's bound adds.
+static int ensure_u16(knn_ctx* ctx, hipStream_t s) {
+  const TrainDev& t = ctx->train;
+  const int DPu = pad_dim_u16l1(t.d);
+  if (DPu <= 0) return knn_fail(KNN_ERR_ARG, "16-bit fixed-point L1 pass supports d <= 256");
+  if (ctx->DPu == DPu) return KNN_OK;
+  int rc;
+  if ((rc = ctx->XU.ensure((size_t)t.n_pad * DPu * sizeof(unsigned short)))) return rc;
+  const int e = t.jx + 5;
+  unsigned long long* st_d = (unsigned long long*)ctx->stats.p + 3;
+  HIP_TRY(hipMemsetAsync(st_d, 0, 8, s));
+  launch_prep_u16_train(t.X64, t.mu, t.n, t.d, DPu, t.n_pad, e, (unsigned short*)ctx->XU.p, st_d, s,
+                        t.perm);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ctx->h_stats + 3, st_d, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(&ctx->u16_dx, &ctx->h_stats[3], 8);
+  ctx->u16_e = e;
+  ctx->DPu = DPu;
   return KNN_OK;
 }
 
@@ -644,6 +672,7 @@ static int ensure_image(knn_ctx* ctx, const SearchPlan& p, hipStream_t s) {
   switch (p.image) {
     case IMG_I8: return ensure_i8(ctx, p.kmetric, s);
     case IMG_I8W: return ensure_i8_wide(ctx, s);
+    case IMG_U16: return ensure_u16(ctx, s);
     case IMG_FP16: return ensure_fp16(ctx, s);
     case IMG_FP16_S3: return ensure_fp16_s3(ctx, s);
     case IMG_BF16X3: return ensure_bf16x3(ctx, s);
@@ -666,7 +695,11 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   const int kmetric = p.kmetric, DP = p.DP, R = p.R, S = p.S, NL = p.NL, C = p.C, n_qt = p.n_qt;
   const int64_t m_pad = p.m_pad;
   const float* const images[] = {t.X32, (const float*)ctx->XB.p, (const float*)ctx->XH.p, nullptr,
-                                 (const float*)ctx->XI.p, (const float*)ctx->XIW.p};
+                                 (const float*)ctx->XI.p, (const float*)ctx->XIW.p,
+                                 (const float*)ctx->XU.p};
+  // the int8 passes (kernel metrics 5-7) share their query builder, centre
+  // and scale; metric 8 takes the fp32 paths' query check and threshold fill
+  const bool i8p = kmetric >= 5 && kmetric <= 7;
   // workspace, sized from the plan
   if ((rc = ctx->Q32.ensure((size_t)m_pad * DP * sizeof(float)))) return rc;
   if ((rc = ctx->qvalid.ensure((size_t)m_pad * sizeof(float)))) return rc;
@@ -729,15 +762,18 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                                (int*)ctx->ord_qpos.p, (int*)ctx->ord_qstart.p, s,
                                ctx->ord_bcnt_zero >= nbc);
     ctx->ord_bcnt_zero = 0;
-    if (kmetric >= 5) bcnt_clear = nbc;
+    if (i8p) bcnt_clear = nbc;
     qperm = (const int*)ctx->ord_qperm.p;
     qpos = (const int*)ctx->ord_qpos.p;
     qstart = (const int*)ctx->ord_qstart.p;
   }
-  if (kmetric < 5)
+  if (!i8p)
     launch_query_check(dQ, t.mu, m, t.d, m_pad, qscale, t.jx,
                        kmetric == 4 ? 65000.0 : std::ldexp(1.0, 100), qvalid, s);
-  if (kmetric >= 5) {  // codes of the train set's grid; a query off it: valid 0 (rescan)
+  if (kmetric == 8)
+    launch_prep_u16_queries(dQ, t.mu, m, t.d, DP, m_pad, ctx->u16_e, (unsigned short*)ctx->Q32.p,
+                            qvalid, s);
+  else if (i8p) {  // codes of the train set's grid; a query off it: valid 0 (rescan)
     launch_prep_i8_queries(dQ, t.mu, qscale, t.jx, DBL_MAX, (const double*)ctx->i8_cent.p, m, t.d,
                            DP, m_pad, ctx->i8_s, (signed char*)ctx->Q32.p, qvalid, s, qperm,
                            p.gthr_init ? (uint32_t*)ctx->gthr.p : nullptr, p.active,
@@ -808,7 +844,7 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
         seeded = true;
       }
     }
-    if (!seeded && kmetric < 5) launch_fill_gthr(cl.gthr, m_pad, p.active, s);
+    if (!seeded && !i8p) launch_fill_gthr(cl.gthr, m_pad, p.active, s);
   }
   if (p.qres) {
     if (!launch_cand_qres((const unsigned short*)ctx->XT16.p, (const float*)ctx->XS16.p,
@@ -828,7 +864,7 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   HIP_TRY(hipGetLastError());
   if (hipEvent_t ev = timing_ev(tc, 2); ev && !p.ev_ext) HIP_TRY(hipEventRecord(ev, s));
   // the rescan / tie counters (the int8 query builder cleared them already)
-  if (kmetric < 5) HIP_TRY(hipMemsetAsync(ctx->rescan_cnt.p, 0, 4 * sizeof(int), s));
+  if (!i8p) HIP_TRY(hipMemsetAsync(ctx->rescan_cnt.p, 0, 4 * sizeof(int), s));
   // per-split certification: a query failing only through some splits'
   // lists rescans just those splits' rows (knn_select.hip)
   SplitMap sm;
@@ -856,7 +892,18 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
     rp.qc8 = (signed char*)ctx->rescan_qc8.p;
     rp.t8 = (long long*)ctx->rescan_t8.p;
   }
-  if (kmetric >= 5) {
+  if (kmetric == 8) {
+    // 16-bit fixed-point L1 proxies are in units of 2^-e; their error is the
+    // two vectors' measured coding errors (the merge rebuilds the query's
+    // codes) plus err_factor(8)'s fp64 rounding terms
+    TrainDev tu = t;
+    tu.jx = ctx->u16_e;
+    ProxyScale ps{qvalid, 0.0, 0.0, false, nullptr, qpos};
+    ps.u16dx = ctx->u16_dx;
+    launch_merge_rerank(metric, (const float*)ctx->cand_v.p, (const int*)ctx->cand_i.p, NL, R, tu,
+                        dQ, m, W, C, err_factor(8, DP), ps, cl.gthr, sink, (int*)ctx->rescan_q.p,
+                        (double*)ctx->rescan_tau.p, (int*)ctx->rescan_cnt.p, sm, rp, s);
+  } else if (i8p) {
     // int8 proxies are exact up to +1 (the odd-norm half of the seed): the
     // merge sees the pass's own centre and scale (codes (x - cent/2^s) 2^s),
     // an absolute error of one code unit (DP x up / DP) and each query's

@@ -85,6 +85,12 @@ struct knn_ctx {
   // DPiw code bytes, n_pad rows (0 = not built)
   DevBuf XIW;
   int DPiw = 0;
+  // the 16-bit fixed-point L1 pass's image (kernel metric 8): rows of DPu
+  // unsigned short codes at scale 2^u16_e, n_pad rows (0 = not built), and
+  // the largest coding error of a row in code units (ProxyScale::u16dx)
+  DevBuf XU;
+  int DPu = 0, u16_e = 0;
+  double u16_dx = 0.0;
   DevBuf smp_x64, smp_xl2, smp_img, smp_scr, smp_v, smp_i;
   // region order: centroids [P][d], chain ranks, region starts, image
   // position <-> train row maps; k-means / sort scratch; per-call query order
@@ -108,7 +114,7 @@ struct knn_ctx {
   // normalisation: per-thread partial max/min, bounds, host-API staging
   DevBuf nrm_part, nrm_mm, nrm_X;
   std::vector<DevBuf*> all_bufs() {
-    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &i8_cent, &i8_gs,
+    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &XU, &i8_cent, &i8_gs,
             &XH,      &XT16,    &XS16,  &mu,      &mu_part, &Q64, &Q32,    &qvalid, &cand_v,   &cand_i,
             &gthr,    &rescan_q, &rescan_tau, &rescan_cnt, &fr_cnt, &fr_buf, &fr_q, &fr_thr,
             &slow_q,  &totals,  &lk, &mrg, &tie_q, &tie_ws, &o_lab, &o_idx, &o_dist, &o_flags, &nrm_part, &nrm_mm, &nrm_X,

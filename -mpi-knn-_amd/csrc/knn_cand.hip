@@ -612,6 +612,7 @@ static void launch_str(const CandLaunch& c, hipStream_t s) {
 
 int cand_blocks_per_cu(int metric, int DP, int R, int nw) {
   if (metric == 7) return DP > 256 ? sad_wide_blocks_per_cu(R, nw) : sad_blocks_per_cu(DP, R, nw);
+  if (metric == 8) return fix16_blocks_per_cu(DP, R, nw);
   if (metric == 2 && bf16x3_streamed(DP)) return s3_blocks_per_cu(R);
   if (metric == 4 && DP > 256) return s3h_blocks_per_cu(R);
 #define KNN_CASE(v) if (DP == v) return blocks_res_##v(R, metric, nw);
@@ -630,7 +631,7 @@ int cand_blocks_per_cu(int metric, int DP, int R, int nw) {
 // queries per wave of the resident kernel serving (metric, DP), from the
 // object that holds that kernel (a variant build's KNN_I8_QB)
 int cand_queries_per_wave(int metric, int DP) {
-  if (metric == 7) return 32;
+  if (metric == 7 || metric == 8) return 32;
 #define KNN_CASE(v) if (DP == v) return qpw_res_##v(metric);
   KNN_DP_LIST(KNN_CASE)
 #undef KNN_CASE
@@ -639,6 +640,7 @@ int cand_queries_per_wave(int metric, int DP) {
 
 int cand_tile_rows(int metric, int DP) {
   if (metric == 7) return DP > 256 ? sad_wide_tile_rows() : sad_tile_rows(DP);
+  if (metric == 8) return fix16_tile_rows(DP);
   if ((metric == 2 && bf16x3_streamed(DP)) || (metric == 4 && DP > 256)) return kS3R;
 #define KNN_CASE(v) if (DP == v) return trows_res_##v(metric);
   KNN_DP_LIST(KNN_CASE)
@@ -648,6 +650,7 @@ int cand_tile_rows(int metric, int DP) {
 
 bool launch_cand(const CandLaunch& c, hipStream_t s) {
   if (c.metric == 7) return c.DP > 256 ? launch_cand_sad_wide(c, s) : launch_cand_sad(c, s);
+  if (c.metric == 8) return launch_cand_fix16(c, s);
 #define KNN_CASE(v) \
   if (c.DP == v) return launch_res_##v(c, s);
   KNN_DP_LIST(KNN_CASE)

@@ -180,6 +180,19 @@ __device__ __forceinline__ _Float16 f16_operand(double v, int jx) {
   return (_Float16)__builtin_ldexp(v, jx);
 }
 
+// The 16-bit fixed-point L1 code of an fp64 value (kernel metric 8): code =
+// clamp(rint(2^e (v - mu)), -32768, 32767) + 32768, and err = |code - 32768 -
+// 2^e (v - mu)|, the value's coding error in code units (y - r is exact
+// unless the clamp acts; +inf for a value whose scaled offset overflows).
+// Shared by the image builders and by the merge, which rebuilds a query's
+// codes to measure its error.
+__device__ __forceinline__ double u16_code(double v, double mu, int e, double& err) {
+  const double y = __builtin_ldexp(v - mu, e);
+  const double r = __builtin_fmin(__builtin_fmax(__builtin_rint(y), -32768.0), 32767.0);
+  err = __builtin_fabs(y - r);
+  return r + 32768.0;
+}
+
 // ------------------------------------------------------- candidate kernel
 // Sorted insertion of v (< L[R-1]) into the ascending register list (L, I);
 // the previous last entry drops out.  Fully unrolled: no dynamic register

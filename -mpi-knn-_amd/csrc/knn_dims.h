@@ -29,6 +29,10 @@ int pad_dim_i8w(int d); // padded dim of the int8 32x32x32 kernel (metric 6), -1
 // padded dim of the wide L1-on-codes image (knn_cand_sad_wide.hip): d in (256, 1024]
 // rounded up to the kernel's 16-dim granule, -1 outside
 int pad_dim_i8l1w(int d);
+// padded dim of the 16-bit fixed-point L1 image (knn_cand_fix16.hip): a
+// multiple of 32 up to 256 (65535 * 256 < 2^24: the sums stay exact floats),
+// -1 beyond
+int pad_dim_u16l1(int d);
 
 #define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
 

@@ -108,7 +108,9 @@ int cand_queries_per_wave(int metric, int DP);  // resident kernel: queries per 
 // 3 = L2 bf16x3 on 16x16x32, 4 = L2 fp16 on 16x16x32, 5 = L2 int8 on
 // 16x16x64, 6 = L2 int8 on 32x32x32 (see knn_cand_res.hip), 7 = L1 on int8
 // codes, v_sad_u8 (knn_cand_sad.hip: X32 = metric 6's int8 image, Q32 = the
-// int8 query codes, xinit = xinit_l1)
+// int8 query codes, xinit = xinit_l1), 8 = L1 on 16-bit fixed-point codes,
+// v_sad_u16 (knn_cand_fix16.hip: X32 = launch_prep_u16_train's rows, Q32 =
+// launch_prep_u16_queries' rows, xinit = xinit_l1)
 struct CandLaunch {
   int metric, DP, R, S, n_qt;
   int64_t n_pad;
@@ -175,6 +177,23 @@ bool sad_wide_dp(int DP);
 bool launch_cand_sad_wide(const CandLaunch& c, hipStream_t s);
 int sad_wide_blocks_per_cu(int R, int nw);
 int sad_wide_tile_rows();
+// kernel metric 8 (knn_cand_fix16.hip; reached through launch_cand and the
+// cand_* queries above): DP of pad_dim_u16l1
+bool launch_cand_fix16(const CandLaunch& c, hipStream_t s);
+int fix16_blocks_per_cu(int DP, int R, int nw);
+int fix16_tile_rows(int DP);
+// Its operands (knn_prep.hip): rows of DP unsigned 16-bit codes
+// clamp(rint(2^e (x - mu)), -32768, 32767) + 32768, zero codes in the pad dims
+// and on pad rows.  Train: n_pad rows, image row p <- train row perm[p];
+// dmax receives the largest row sum of |code - 32768 - 2^e (x - mu)| (code
+// units, fp64 bits, atomicMax: clear it first).  Queries: m_pad rows, a query
+// with valid[q] <= 0 gets zero codes.
+void launch_prep_u16_train(const double* X64, const double* mu, int64_t n, int d, int DP,
+                           int64_t n_pad, int e, unsigned short* out, unsigned long long* dmax,
+                           hipStream_t s, const int* perm = nullptr);
+void launch_prep_u16_queries(const double* Q64, const double* mu, int64_t m, int d, int DP,
+                             int64_t m_pad, int e, unsigned short* out, const float* valid,
+                             hipStream_t s);
 // gthr: the candidate kernel's per-query global thresholds ([m_pad][kGthrSlots] keys)
 // or null when the kernel kept none
 // failed queries are appended to rescan_q with rescan_tau = the W-th exact
@@ -201,6 +220,11 @@ struct ProxyScale {
   // reads it instead of the fp64 rows (merge_rerank_kernel, exact_sorted_i8)
   const signed char* i8x = nullptr;
   int i8rb = 0, i8dp = 0, i8swz = 0;
+  // 16-bit fixed-point L1 pass (kernel metric 8; t.jx = the code scale e):
+  // the largest coding error of a train row, max over rows of SUM_c |code -
+  // 32768 - 2^e (x_c - mu_c)| in code units (< 0: another pass).  The merge
+  // rebuilds the query's codes and measures its own sum.
+  double u16dx = -1.0;
 };
 // Per-split certification (merge) and the targeted rescan: a query whose
 // bound fails only through some splits' lists (a list holding R of its top

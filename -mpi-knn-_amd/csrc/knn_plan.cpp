@@ -59,6 +59,11 @@ int pad_dim_i8l1w(int d) {
   return d > 256 && d <= 1024 ? (d + 15) / 16 * 16 : -1;
 }
 
+// L1 on 16-bit fixed-point codes (knn_cand_fix16.hip): the resident widths
+// that are multiples of 32, up to 256 -- the integer sums stay below 65535 *
+// 256 < 2^24, exact as floats
+int pad_dim_u16l1(int d) { return pad_dim_i8w(d); }
+
 // fp16 S3 kernel above 256 dims: any multiple of 32
 int pad_dim_fp16_s3(int d) {
   const int DP = (d + 31) / 32 * 32;
@@ -216,6 +221,16 @@ static bool use_i8l1(const PlanIn& in) {
   return in.m >= 4096 && in.W <= kQuadMaxW;
 }
 
+// L1 on 16-bit fixed-point codes (kernel metric 8, knn_cand_fix16.hip): any
+// train set at d <= 256 under the L1 metric.  Tuning key "u16l1": 0 off (the
+// default), 1 on at every batch size.  Opt-in only: AUTO never chooses it
+// (DESIGN.md §4 has the measurement a change of AUTO would rest on).  Where
+// "i8l1" puts an integer-coded train set on the exact byte-code pass (metric
+// 7, either form), that pass wins: plan_search asks use_i8l1 first.
+static bool use_u16l1(const PlanIn& in) {
+  return in.metric == KNN_METRIC_L1 && in.tune.u16l1 == 1 && pad_dim_u16l1(in.d) > 0;
+}
+
 static bool use_bf16x3(const PlanIn& in) {
   if (in.metric != KNN_METRIC_L2) return false;
   if (in.precision == KNN_PRECISION_FP32) return false;
@@ -231,6 +246,10 @@ static bool resident_variant(int DP, int R, int M, int NW) {
   if (M == 7)
     return (pad_dim_i8w(DP) == DP || pad_dim_i8l1w(DP) == DP) && (R == 8 || R == 16) &&
            (NW == 4 || NW == 8);
+  // metric 8 (knn_cand_fix16.hip): DP of pad_dim_u16l1, R in {8, 16}, 4 waves,
+  // or 8 up to DP = 128 (the resident query takes DP / 2 registers)
+  if (M == 8)
+    return pad_dim_u16l1(DP) == DP && (R == 8 || R == 16) && (NW == 4 || (NW == 8 && DP <= 128));
   return (M != 2 || DP % 16 == 0) && (M != 1 || (NW == 4 && R != 4)) &&
          (M < 3 || (DP % 32 == 0 && (R == 4 || (M >= 5 && R == 8)) && (NW == 8 || M >= 4))) &&
          (NW != 16 || M == 4) && (M != 5 || (DP % 64 == 0 && (NW == 8 || NW == 4))) &&
@@ -276,7 +295,7 @@ static void choose_geometry(const PlanIn& in, SearchPlan& p) {
   if (p.s3q) S_hi = std::min(S_hi, kMaxUnion / (4 * 8));
   for (int R : {4, 8, 16}) {
     if (!list_len_ok(R)) continue;
-    if (R == 4 && (DP > 256 || metric == 1 || metric == 7)) continue;
+    if (R == 4 && (DP > 256 || metric == 1 || metric == 7 || metric == 8)) continue;
     const int64_t slots = (int64_t)(p.s3q ? in.facts.s3q_blocks_per_cu()
                                           : in.facts.cand_blocks_per_cu(metric, DP, R, p.nw)) *
                           in.cu_count;
@@ -361,6 +380,12 @@ SearchPlan plan_search(const PlanIn& in) {
     p.kmetric = 7;
     p.image = IMG_I8W;
     p.DP = pad_dim_i8l1w(in.d);
+  } else if (use_u16l1(in)) {
+    // L1 on 16-bit fixed-point codes of the centred rows, its own image; one
+    // list per lane as the fp32 L1 kernel
+    p.kmetric = 8;
+    p.image = IMG_U16;
+    p.DP = pad_dim_u16l1(in.d);
   } else if (use_i8(in)) {
     p.kmetric = i8_kernel_d(tune, in.d);
     p.image = IMG_I8;
@@ -394,6 +419,9 @@ SearchPlan plan_search(const PlanIn& in) {
   else if (kmetric == 6 && tune.nw == 16) p.nw = 16;
   // L1 on int8 codes: 4 or 8 (256 queries share each staged tile)
   else if (kmetric == 7) p.nw = tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4);
+  // L1 on 16-bit codes: 8 only up to DP = 128 (no 8-wave kernel above it)
+  else if (kmetric == 8)
+    p.nw = DP > 128 ? 4 : (tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4));
   else if (kmetric >= 3) p.nw = 8;  // (the 16x16 layouts: fp16, bf16x3, int8)
   else if (DP <= 256 && kmetric != 1) p.nw = tune.nw ? std::min(tune.nw, 8) : (m >= 4096 ? 8 : 4);
   else p.nw = 4;
@@ -464,12 +492,13 @@ SearchPlan plan_search(const PlanIn& in) {
   // (metric 7 takes its queries in call order and starts every stream at the
   // split's first tile: a train set laid out by region or in norm blocks is
   // just another row order to it -- lists carry image positions either way)
-  p.query_order = in.ord_P > 0 && tune.order != 0 && !p.s3 && kmetric >= 4 && kmetric != 7 && DP <= 256;
+  // (metric 8 likewise)
+  p.query_order = in.ord_P > 0 && tune.order != 0 && !p.s3 && kmetric >= 4 && kmetric < 7 && DP <= 256;
   p.ophase = std::min(tune.ophase < 0 ? kOrderPhases : tune.ophase, in.ord_P);
   // the int8 image's chunks are swizzled for the 16x16x64 kernel, plain for
   // 32x32x32; the fp16 image's as tuning "xhswz" says (only the metric 4 and
   // 5 kernels read xsw)
-  p.i8_swz = kmetric == 6 || kmetric == 7 ? 0 : 1;
+  p.i8_swz = kmetric >= 6 ? 0 : 1;
   p.xsw = kmetric >= 5 ? p.i8_swz : tune.xhswz != 0;
   // the int8 rescan filter (metric 6's plain image; knn_select.hip)
   // (tuning key "i8resc": -1 / 1 auto, 0 every failed query on the fp32 filter)
@@ -501,6 +530,9 @@ SearchPlan plan_search(const PlanIn& in) {
     else
       snprintf(p.kernel, sizeof p.kernel, "cand_sad_kernel<%d,%d,%d>", DP, p.R, p.nw);
     p.ok = resident_variant(DP, p.R, kmetric, p.nw);
+  } else if (kmetric == 8) {
+    snprintf(p.kernel, sizeof p.kernel, "cand_fix16_kernel<%d,%d,%d>", DP, p.R, p.nw);
+    p.ok = resident_variant(DP, p.R, kmetric, p.nw);
   } else if (DP <= 256) {
     snprintf(p.kernel, sizeof p.kernel, "cand_kernel<%d,%d,%d,%d>", DP, p.R, kmetric, p.nw);
     p.ok = cand_supported(DP) && resident_variant(DP, p.R, kmetric, p.nw);
@@ -522,8 +554,15 @@ SearchPlan plan_search(const PlanIn& in) {
 //     error is measured (train: TrainDev::dxmax, queries: by the merge from
 //     the operands themselves) and added by the merge with the seed's own
 //     rounding and the fp16 subnormal-range terms.
+//   kmetric 8 (16-bit fixed-point L1): the integer sums are exact; the
+//     coding error itself is measured (the merge adds 2^-e (Dq + Dx),
+//     ProxyScale::u16dx).  What remains is fp64 rounding, relative to ||q -
+//     mu||_1 + max||x - mu||_1 >= the distance: v - mu before the coding (u64
+//     = 2^-53 per element, on both sides) and the reference's own loop (a
+//     subtraction and DP - 1 additions: gamma_DP) -- (DP + 4) u64, doubled.
 double err_factor(int kmetric, int DP) {
   if (kmetric == 7) return 0.0;  // integer sums of code differences: exact
+  if (kmetric == 8) return 2.0 * (DP + 4) * std::ldexp(1.0, -53);
   const double u = std::ldexp(1.0, -24);
   if (kmetric == 4) {
     const double u2 = std::ldexp(1.0, -23);
@@ -567,6 +606,7 @@ const TuneKey kTuneKeys[] = {
     {"i8", &Tuning::i8, -1, 1, nullptr, "i8 must be -1, 0 or 1"},
     {"i8w", &Tuning::i8w, -1, 1, nullptr, "i8w must be -1, 0 or 1"},
     {"i8l1", &Tuning::i8l1, -1, 2, nullptr, "i8l1 must be -1, 0, 1 or 2 (2: also at 256 < d <= 1024)"},
+    {"u16l1", &Tuning::u16l1, 0, 1, nullptr, "u16l1 must be 0 or 1"},
     {"s3gq", &Tuning::s3gq, 0, 0, kSetS3gq, "s3gq must be 0 (auto) or 1, 2, 4, 8, 16, 32"},
     {"ophase", &Tuning::ophase, -1, kRegionMax, nullptr, "ophase must be -1 (auto) .. 64"},
     {"order", &Tuning::order, -1, kRegionMax, nullptr,

@@ -601,6 +601,77 @@ void launch_prep_i8_rows(const double* X64, const double* cent, int64_t n, int d
                      DP, n_pad, s, out, perm);
 }
 
+// -------------------- 16-bit fixed-point L1 images (kernel metric 8, d <= 256)
+// code = clamp(rint(2^e (v - mu)), -32768, 32767) + 32768 per dim, one scale
+// 2^e for all dims (knn_cand_fix16.hip; u16_code, knn_device.h).
+
+// Train rows: DP codes per row (0 in the pad dims and on pad rows), one wave
+// per row; the largest row sum of the coding errors |code - 32768 - 2^e (x -
+// mu)| (code units; fp64, non-negative -> ordered as u64 bits) into dmax.
+__global__ void __launch_bounds__(256)
+prep_u16_train_kernel(const double* __restrict__ X64, const double* __restrict__ mu, int64_t n,
+                      int d, int DP, int64_t n_pad, int e, unsigned short* __restrict__ out,
+                      unsigned long long* __restrict__ dmax, const int* __restrict__ perm) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  double m = 0.0;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_pad; row += wstride) {
+    const int64_t src = src_row(perm, row, n);
+    double dsum = 0.0;
+    for (int c = lane; c < DP; c += 64) {
+      unsigned short k = 0;
+      if (row < n && c < d) {
+        double er;
+        k = (unsigned short)(int)u16_code(X64[src * d + c], mu[c], e, er);
+        dsum += er;
+      }
+      out[row * DP + c] = k;
+    }
+    m = fmax(m, wave_sum_d(dsum));
+  }
+  // (small relative slack covers the order of the fp64 sums above)
+  if (lane == 0) atomicMax(dmax, (unsigned long long)__double_as_longlong(m * (1.0 + 1e-12)));
+}
+
+void launch_prep_u16_train(const double* X64, const double* mu, int64_t n, int d, int DP,
+                           int64_t n_pad, int e, unsigned short* out, unsigned long long* dmax,
+                           hipStream_t s, const int* perm) {
+  int64_t blocks = (n_pad + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(prep_u16_train_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X64, mu, n, d,
+                     DP, n_pad, e, out, dmax, perm);
+}
+
+// Query rows: the same codes; a query launch_query_check marked void or
+// non-finite (valid[row] <= 0) gets zero codes, i.e. finite proxies the merge
+// ignores.
+__global__ void __launch_bounds__(256)
+prep_u16_queries_kernel(const double* __restrict__ Q64, const double* __restrict__ mu, int64_t m,
+                        int d, int DP, int64_t m_pad, int e, unsigned short* __restrict__ out,
+                        const float* __restrict__ valid) {
+  const int64_t total = m_pad * DP;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / DP;
+    const int c = (int)(i - row * DP);
+    unsigned short k = 0;
+    if (row < m && c < d && valid[row] > 0.0f) {
+      double er;
+      k = (unsigned short)(int)u16_code(Q64[row * d + c], mu[c], e, er);
+    }
+    out[i] = k;
+  }
+}
+
+void launch_prep_u16_queries(const double* Q64, const double* mu, int64_t m, int d, int DP,
+                             int64_t m_pad, int e, unsigned short* out, const float* valid,
+                             hipStream_t s) {
+  int64_t blocks = (m_pad * DP + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(prep_u16_queries_kernel, dim3((unsigned)blocks), dim3(256), 0, s, Q64, mu, m,
+                     d, DP, m_pad, e, out, valid);
+}
+
 __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
     p[e] = v;

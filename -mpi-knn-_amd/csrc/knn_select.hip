@@ -460,6 +460,24 @@ merge_rerank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, in
       }
       off_grid = __ballot(off) != 0;
     }
+    // L1 on 16-bit fixed-point codes (kernel metric 8; t.jx = the code scale
+    // e): |2^-e proxy - SUM|q - x|| <= 2^-e (Dq + Dx) with D the sum of a
+    // vector's coding errors |code - 32768 - 2^e (v - mu)|.
+    // Dq is measured on the query's codes, rebuilt here exactly as
+    // prep_u16_queries_kernel builds them (a clamped coordinate makes it
+    // large, an overflowing one +inf: the query then fails certification);
+    // Dx is the image builder's maximum over the train rows.  f_err covers
+    // the fp64 rounding of v - mu and of the reference's own loop.
+    if (METRIC == 1 && ps.u16dx >= 0.0) {
+      double dq = 0.0;
+      for (int c = lane; c < d; c += 64) {
+        double er;
+        (void)u16_code(qv[c], t.mu[c], t.jx, er);
+        dq += er;
+      }
+      dq = wave_sum_d(dq);
+      E += __builtin_ldexp((dq + ps.u16dx) * (1.0 + 1e-12), -t.jx);
+    }
     // proxies are in scaled units (operands 2^jx (x - mu), knn_prep.hip):
     // unscale exactly; operand values outside the format's normal range add
     // absolute error terms (ue per element, up per product, scaled units)

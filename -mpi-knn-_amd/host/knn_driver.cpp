@@ -15,7 +15,8 @@
 // --threads T (CSV parsing threads), --output path, --timings (per-phase
 // seconds on stderr; stdout stays the reference's), --tune KEY=VALUE (a
 // tuning key of the library, knn_set_tuning; repeatable -- e.g. --tune i8l1=1
-// for the Manhattan pass on int8 codes of byte-valued CSVs),
+// for the Manhattan pass on int8 codes of byte-valued CSVs, --tune u16l1=1
+// for the one on 16-bit fixed-point codes of any data, normalised included),
 // --K_list k1,k2,... (needs --Validation true): the validation pass scores
 // every K of the list from one search (knn_group_classify_sweep), prints
 // "K = <k> accuracy = <acc>" per K in list order, selects the first K whose
@@ -80,7 +81,8 @@ void usage() {
           "  (no validation file is read)\n"
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
           "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
-          "  (i8l1=2: also at 256 < dim <= 1024)\n");
+          "  (i8l1=2: also at 256 < dim <= 1024); --tune u16l1=1: the L1 pass on 16-bit\n"
+          "  fixed-point codes for any data at dim <= 256 (--Normalize true included)\n");
 }
 
 // "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit

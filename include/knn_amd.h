@@ -346,6 +346,19 @@ int knn_last_geometry(knn_ctx* ctx, int64_t out[4]);
  * d > 256 (MNIST's 784 included) stays on the fp32 stream kernel unless
  * "i8l1" = 2 asks for the wide form of the pass, which serves 256 < d <= 1024
  * (opt-in: never AUTO's choice).
+ * Any other L1 call at d <= 256 -- real-valued data, byte data after the
+ * reference's Normalize = true (x / 255 is on no binary grid) -- can take a
+ * lossy-but-certified pass on 16-bit fixed-point codes (kernel path 8:
+ * v_sad_u16, two dims per lane per instruction).  Codes are clamp(rint(2^e (v
+ * - mean)), -32768, 32767) + 32768 with one power-of-two scale for all
+ * dimensions, chosen so the train rows take half the code range; the proxy's
+ * error is at most 2^-e times the two vectors' summed coding errors, which
+ * the library measures (train rows when the image is built, each query in
+ * the merge) and certifies against; a query clamped far outside the train
+ * set's range fails certification and goes to the exact rescan.  Results are
+ * unchanged.  Tuning key "u16l1": 0 off (the default), 1 on at every batch
+ * size; opt-in only, AUTO never chooses it; where "i8l1" selects path 7 for
+ * an integer-coded train set, that exact pass wins.
  * Environment override at knn_create: KNN_PRECISION=fp32|bf16x3|fp16. */
 #define KNN_PRECISION_AUTO 0
 #define KNN_PRECISION_FP32 1
@@ -355,7 +368,8 @@ int knn_set_precision(knn_ctx* ctx, int mode);
 /* Candidate kernel flavour of the last search: 0 fp32 L2, 1 fp32 L1, 2 bf16x3
  * L2 (32x32x16 MFMA), 3 bf16x3 L2 (16x16x32), 4 fp16 L2 (16x16x32), 5 int8
  * L2 (16x16x64, exact integer dot products), 6 int8 L2 (32x32x32), 7 L1 on
- * int8 codes (v_sad_u8, exact integer sums; d <= 256). */
+ * int8 codes (v_sad_u8, exact integer sums; d <= 256, or <= 1024 with "i8l1"
+ * = 2), 8 L1 on 16-bit fixed-point codes (v_sad_u16, certified; d <= 256). */
 int knn_last_candidate_path(knn_ctx* ctx);
 /* Name of the last candidate kernel launched, as rocprofv3 reports it
  * without namespace, spaces and argument list (e.g. "cand_kernel<128,4,4,8>"). */
@@ -372,7 +386,10 @@ const char* knn_last_kernel_name(knn_ctx* ctx);
  * "i8l1" (the L1 pass on int8 codes, path 7, where the train set is
  * integer-coded and d <= 256: 0 off, 1 on at every batch size, -1 auto; 2: as
  * 1, and also at 256 < d <= 1024 on the wide kernel, cand_sad_wide_kernel --
- * beyond 1024 dims, off the grid or under L2 it plans what 0 plans), "i8w" (int8
+ * beyond 1024 dims, off the grid or under L2 it plans what 0 plans), "u16l1"
+ * (no auto: 0 off, the default; 1 the L1 pass on 16-bit fixed-point codes,
+ * path 8, for any train set at d <= 256 and every batch size, except where
+ * "i8l1" selects path 7; it moves no L2 call and no call at d > 256), "i8w" (int8
  * kernel: -1 auto, 0 the 16x16x64 one, 1 the 32x32x32 one; also read by
  * knn_set_train*, whose norm blocks interleave the rows over that kernel's
  * lane lists -- set it before the train set: a later change keeps results
