@@ -350,6 +350,20 @@ static void choose_geometry(const PlanIn& in, SearchPlan& p) {
       for (int S = bS + 1; S <= S_hi && bq < gmax; S++)
         if (eff_of(S) >= best - 0.02 && s3_group(n_qt, S, gmax) > bq) { bS = S; bq = s3_group(n_qt, S, gmax); }
     }
+    // L1 on int8 codes over a norm-blocked image (knn_order.hip): a window's
+    // sub-tiles in norm order sit one 256-row tile apart (norm_spread), i.e.
+    // 2 or 4 of this kernel's tiles, and the rows near a query in L1 have
+    // nearly its code norm.  An even S sends such a band to half of the
+    // splits (tile mod S keeps its parity) and its lists overflow: 63 of 96
+    // queries failed certification at W = 512, n = 20000, d = 48 with S = 44,
+    // 26 with S = 64, against 5 in train order (profiles/ab_log.md, "l1kcap").
+    // R = 16 has no share rule to absorb that (R = 8 keeps 0.8 per list), so
+    // it takes the largest odd S: every split sees the band, over the most
+    // lists the union allows.
+    if (metric == 7 && in.ord_nb && R == 16 && S_hi >= 3) {
+      const int odd = S_hi - (S_hi % 2 == 0);
+      if (odd >= S_lo) bS = odd;
+    }
     if (tune.S) bS = std::min(tune.S, S_hi);
     bestS = bS;
     bestR = R;
