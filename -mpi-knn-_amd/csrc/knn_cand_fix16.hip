@@ -18,33 +18,17 @@
 // 1) with proxies in units of 2^-e.  Pad dims hold code 0 on both sides and
 // add nothing; a pad row's seed (xinit_l1) is +inf.
 //
-// Lane (j = lane & 31, h = lane >> 5) of wave w owns query j of the wave and
-// the rows (i & 3) + 8 (i >> 2) + 4h of every 32-row sub-tile, as metrics 1
-// and 7 (knn_cand_sad.hip, whose structure this kernel keeps): select_block,
-// write_lists and the merge's 2-lists-per-split layout apply unchanged.  The
-// query's codes stay in DP / 2 VGPRs -- 128 at DP = 256, which is why the
-// 8-wave form (256 registers per lane) exists only up to DP = 128; wider rows
-// run 4 waves (512 per lane).  A tile (64 rows, 128 at DP <= 64: at most 64 KB
-// of LDS for the two buffers) is staged through registers at a row stride of
-// 2 DP bytes; the tile after it is in flight (global loads) behind the
-// current tile's compute, one barrier per tile.  Every ds_read_b128 of the
-// loop has two distinct addresses per wave (one per h), in different 16-lane
-// groups: conflict-free at any stride.  Per 8 dims of a (query, row) pair the
-// loop issues one ds_read_b128 and four v_sad_u16.
-#include "knn_device.h"
-
-#include <hip/hip_ext.h>
+// The structure is knn_cand_codes.h's.  The query's codes stay in DP / 2
+// VGPRs -- 128 at DP = 256, which is why the 8-wave form (256 registers per
+// lane) exists only up to DP = 128; wider rows run 4 waves (512 per lane).  A
+// tile is 64 rows, 128 at DP <= 64 (at most 64 KB of LDS for the two
+// buffers), at a row stride of 2 DP bytes.  Per 8 dims of a (query, row) pair
+// the loop issues one ds_read_b128 and four v_sad_u16.
+#include "knn_cand_codes.h"
 
 namespace knnk {
 
 constexpr int fix16_tile_rows_c(int DP) { return DP > 64 ? 64 : 128; }
-
-// tiles at which a workgroup publishes its lists' thresholds and fetches the
-// query's slots (cand_kernel's schedule: early at 0, 1, 2, 4, then every 8th)
-__device__ __forceinline__ bool fix16_exchange_tile(int it) {
-  if (it < 8) return it == 0 || it == 1 || it == 2 || it == 4;
-  return (it & 7) == 7;
-}
 
 template <int DP, int R, int NW>
 __global__ void __launch_bounds__(NW * 64)
@@ -90,34 +74,15 @@ cand_fix16_kernel(const uint4* __restrict__ X16, const uint4* __restrict__ Q16,
   }
   float thr = KNN_INF_F, tq = KNN_INF_F;
   uint32_t last_pub = kKeyInf;
-  // this query's threshold slots (cand_kernel: "Global per-query threshold");
-  // lane (j, h) fetches slots 4h .. 4h + 3, the split publishes into slot
-  // split & gmask
   uint32_t* gq = gthr ? gthr + qg * kGthrSlots : nullptr;
 
   const int my_nt = split < n_tiles ? (n_tiles - split + S - 1) / S : 0;
 
-  // staging: the tile's chunks are contiguous in the image (rows of CPR
-  // chunks, no pad); this thread's chunks e = tid, tid + NT, ...
-  uint4 st[NPT];
-  float sxv = 0.0f;
+  CodeStage<NT, NPT, TR, 0, NCH % NT == 0> stg;
   auto load_tile = [&](int t) {
-    const uint4* g = X16 + (int64_t)t * NCH;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int e = tid + u * NT;
-      if (NCH % NT == 0 || e < NCH) st[u] = g[e];
-    }
-    if (tid < TR) sxv = xinit[(int64_t)t * TR + tid];
+    stg.load(X16 + (int64_t)t * NCH, xinit, t, tid, NCH);
   };
-  auto store_tile = [&](int b) {
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int e = tid + u * NT;
-      if (NCH % NT == 0 || e < NCH) lds[b][e] = make_uint4(st[u].x, st[u].y, st[u].z, st[u].w);
-    }
-    if (tid < TR) sx[b][tid] = sxv;
-  };
+  auto store_tile = [&](int b) { stg.store(lds[b], sx[b], tid, NCH); };
 
   if (my_nt > 0) {
     load_tile(split);
@@ -128,33 +93,9 @@ cand_fix16_kernel(const uint4* __restrict__ X16, const uint4* __restrict__ Q16,
   for (int it = 0; it < my_nt; ++it) {
     const int t = split + it * S;
     const int cur = it & 1;
-    // the exchange: publish the lists' threshold (one lane per query, only
-    // when it improved) and fetch the slots; they are read after the tile's
-    // compute.  A fetched value that is stale is larger: still a valid bound.
-    const bool xch = gq && it + 1 < my_nt && fix16_exchange_tile(it);
+    const bool xch = gq && it + 1 < my_nt && code_exchange_tile(it);
     uint32_t gmx = 0;
-    if (xch) {
-      float mv;
-      if (gk) {
-        // the gk-th smallest of the union of the query's two lists here
-        float u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = L[e];
-        mv = union_kth<2>(u, gk);
-      } else {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr), __float_as_uint(thr),
-                                                         false, false);
-        mv = __builtin_fminf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      }
-      const uint32_t pk = f2key(mv);
-      if (h == 0 && pk < last_pub) {
-        atomicMin(gq + (split & gmask), pk);
-        last_pub = pk;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        gmx = max(gmx, __hip_atomic_load(gq + 4 * h + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
+    if (xch) gmx = code_publish_fetch<R>(L, thr, last_pub, gq, gk, h, split, gmask);
     if (it + 1 < my_nt) load_tile(t + S);
 
 #pragma unroll 1
@@ -166,49 +107,24 @@ cand_fix16_kernel(const uint4* __restrict__ X16, const uint4* __restrict__ Q16,
 #pragma unroll
       for (int c = 0; c < CPR; ++c) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const uint4 x = base[((i & 3) + 8 * (i >> 2)) * CPR + c];
-          uint32_t a = acc[i];
-          a = __builtin_amdgcn_sad_u16(x.x, q[4 * c + 0], a);
-          a = __builtin_amdgcn_sad_u16(x.y, q[4 * c + 1], a);
-          a = __builtin_amdgcn_sad_u16(x.z, q[4 * c + 2], a);
-          a = __builtin_amdgcn_sad_u16(x.w, q[4 * c + 3], a);
-          acc[i] = a;
-        }
+        for (int i = 0; i < 16; ++i)
+          acc[i] = code_sad4<SadU16>(base[code_row(i) * CPR + c], &q[4 * c], acc[i]);
       }
       // (the sums are below 2^24: exact floats; a pad row's seed makes it +inf)
       f32x16 av;
       const float* sr = &sx[cur][sub * kTR + 4 * h];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[(i & 3) + 8 * (i >> 2)];
+      for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[code_row(i)];
       select_block<R>(av, (t * (TR / kTR) + sub) * kTR, h, L, I, thr, tq);
     }
 
-    if (xch) {
-      // lanes l and l ^ 32 hold the two halves of the query's slots
-      const auto sw = __builtin_amdgcn_permlane32_swap(gmx, gmx, false, false);
-      tq = __builtin_fminf(tq, key2f(max(sw[0], sw[1])));
-    }
+    if (xch) tq = __builtin_fminf(tq, code_fetched(gmx));
     if (it + 1 < my_nt) store_tile(cur ^ 1);
     // the next tile is in LDS for every wave, and every wave is done reading
     // this one before tile it + 2 is stored over it
     __syncthreads();
   }
   write_lists<R>(out_v, out_i, qg, S, split, h, L, I);
-}
-
-template <int DP, int R, int NW>
-static void launch_fix16(const CandLaunch& c, hipStream_t s) {
-  const int nt = (int)(c.n_pad / fix16_tile_rows_c(DP));
-  const dim3 grid((unsigned)(c.n_qt * c.S)), block(NW * 64);
-  if (c.ev_start)
-    hipExtLaunchKernelGGL((cand_fix16_kernel<DP, R, NW>), grid, block, 0, s, c.ev_start, c.ev_stop,
-                          0, (const uint4*)c.X32, (const uint4*)c.Q32, c.xinit, nt, c.S, c.n_qt,
-                          c.out_v, c.out_i, c.gthr, c.gk, c.gmask);
-  else
-    hipLaunchKernelGGL((cand_fix16_kernel<DP, R, NW>), grid, block, 0, s, (const uint4*)c.X32,
-                       (const uint4*)c.Q32, c.xinit, nt, c.S, c.n_qt, c.out_v, c.out_i, c.gthr,
-                       c.gk, c.gmask);
 }
 
 // Instantiated: DP = pad_dim_u16l1's values, R in {8, 16}, 4 waves, and 8
@@ -219,25 +135,17 @@ static void launch_fix16(const CandLaunch& c, hipStream_t s) {
 
 template <class F>
 static bool fix16_dispatch(int DP, int R, int nw, F f) {
-  if ((R != 8 && R != 16) || (nw != 4 && nw != 8)) return false;
-  using std::integral_constant;
-#define KNN_CASE4(v)                                                                      \
-  if (DP == v && nw == 4) {                                                               \
-    if (R == 8) f(integral_constant<int, v>{}, integral_constant<int, 8>{}, integral_constant<int, 4>{});  \
-    else f(integral_constant<int, v>{}, integral_constant<int, 16>{}, integral_constant<int, 4>{});        \
-    return true;                                                                          \
-  }
-#define KNN_CASE8(v)                                                                      \
-  if (DP == v && nw == 8) {                                                               \
-    if (R == 8) f(integral_constant<int, v>{}, integral_constant<int, 8>{}, integral_constant<int, 8>{});  \
-    else f(integral_constant<int, v>{}, integral_constant<int, 16>{}, integral_constant<int, 8>{});        \
-    return true;                                                                          \
-  }
+#define KNN_CASE(v, w) \
+  if (DP == v && nw == w) \
+    return code_dispatch_r(R, [&](auto r) { f(code_ic<v>{}, r, code_ic<w>{}); });
+#define KNN_CASE4(v) KNN_CASE(v, 4)
+#define KNN_CASE8(v) KNN_CASE(v, 8)
   KNN_FIX16_NARROW(KNN_CASE4)
   KNN_FIX16_WIDE(KNN_CASE4)
   KNN_FIX16_NARROW(KNN_CASE8)
-#undef KNN_CASE4
 #undef KNN_CASE8
+#undef KNN_CASE4
+#undef KNN_CASE
   return false;
 }
 
@@ -246,7 +154,8 @@ bool launch_cand_fix16(const CandLaunch& c, hipStream_t s) {
   // the image a whole number of tiles
   if (c.qpb != c.nw * 32 || !c.xinit || c.n_pad % 128) return false;
   return fix16_dispatch(c.DP, c.R, c.nw, [&](auto dp, auto r, auto nw) {
-    launch_fix16<dp.value, r.value, nw.value>(c, s);
+    launch_code_kernel(cand_fix16_kernel<dp.value, r.value, nw.value>, c, s,
+                       (int)(c.n_pad / fix16_tile_rows_c(dp.value)));
   });
 }
 

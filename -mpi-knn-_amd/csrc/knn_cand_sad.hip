@@ -22,30 +22,15 @@
 // read it; a second, unsigned image would cost n (DP + 16) bytes of HBM for
 // the same effect).  Zero pad dims are 0x80 on both sides: no contribution.
 //
-// Lane (j = lane & 31, h = lane >> 5) of wave w owns query j of the wave and
-// the rows (i & 3) + 8 (i >> 2) + 4h of every 32-row sub-tile, as metric 1:
-// select_block, write_lists and the merge's 2-lists-per-split layout apply
-// unchanged.  The query's codes stay in DP / 4 VGPRs.  A tile (128 rows, 64
-// at DP > 128) is staged through registers into one of two LDS buffers at a
-// row stride of DP bytes; the tile after it is in flight (global loads)
-// behind the current tile's compute, one barrier per tile.  Every
-// ds_read_b128 of the loop has two distinct addresses per wave (one per h),
-// in different 16-lane groups: conflict-free at any stride.  Per 16 dims of a
-// (query, row) pair the loop issues one ds_read_b128 and four v_sad_u8.
-#include "knn_device.h"
-
-#include <hip/hip_ext.h>
+// The structure is knn_cand_codes.h's.  The query's codes stay in DP / 4
+// VGPRs; a tile is 128 rows, 64 at DP > 128, at a row stride of DP bytes in
+// LDS.  Per 16 dims of a (query, row) pair the loop issues one ds_read_b128
+// and four v_sad_u8.
+#include "knn_cand_codes.h"
 
 namespace knnk {
 
 constexpr int sad_tile_rows_c(int DP) { return DP > 128 ? 64 : 128; }
-
-// tiles at which a workgroup publishes its lists' thresholds and fetches the
-// query's slots (cand_kernel's schedule: early at 0, 1, 2, 4, then every 8th)
-__device__ __forceinline__ bool sad_exchange_tile(int it) {
-  if (it < 8) return it == 0 || it == 1 || it == 2 || it == 4;
-  return (it & 7) == 7;
-}
 
 template <int DP, int R, int NW>
 __global__ void __launch_bounds__(NW * 64)
@@ -93,15 +78,13 @@ cand_sad_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   }
   float thr = KNN_INF_F, tq = KNN_INF_F;
   uint32_t last_pub = kKeyInf;
-  // this query's threshold slots (cand_kernel: "Global per-query threshold");
-  // lane (j, h) fetches slots 4h .. 4h + 3, the split publishes into slot
-  // split & gmask
   uint32_t* gq = gthr ? gthr + qg * kGthrSlots : nullptr;
 
   const int my_nt = split < n_tiles ? (n_tiles - split + S - 1) / S : 0;
 
   // staging: chunk e = (row e / CPR, chunk e % CPR) of the tile, this
-  // thread's chunks e = tid, tid + NT, ...
+  // thread's chunks e = tid, tid + NT, ... (the image's rows carry a pad
+  // chunk, so not CodeStage: through it the index arithmetic compiles differently)
   uint4 st[NPT];
   float sxv = 0.0f;
   auto load_tile = [&](int t) {
@@ -132,33 +115,9 @@ cand_sad_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   for (int it = 0; it < my_nt; ++it) {
     const int t = split + it * S;
     const int cur = it & 1;
-    // the exchange: publish the lists' threshold (one lane per query, only
-    // when it improved) and fetch the slots; they are read after the tile's
-    // compute.  A fetched value that is stale is larger: still a valid bound.
-    const bool xch = gq && it + 1 < my_nt && sad_exchange_tile(it);
+    const bool xch = gq && it + 1 < my_nt && code_exchange_tile(it);
     uint32_t gmx = 0;
-    if (xch) {
-      float mv;
-      if (gk) {
-        // the gk-th smallest of the union of the query's two lists here
-        float u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = L[e];
-        mv = union_kth<2>(u, gk);
-      } else {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr), __float_as_uint(thr),
-                                                         false, false);
-        mv = __builtin_fminf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      }
-      const uint32_t pk = f2key(mv);
-      if (h == 0 && pk < last_pub) {
-        atomicMin(gq + (split & gmask), pk);
-        last_pub = pk;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        gmx = max(gmx, __hip_atomic_load(gq + 4 * h + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
+    if (xch) gmx = code_publish_fetch<R>(L, thr, last_pub, gq, gk, h, split, gmask);
     if (it + 1 < my_nt) load_tile(t + S);
 
 #pragma unroll 1
@@ -170,29 +129,18 @@ cand_sad_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
 #pragma unroll
       for (int c = 0; c < CPR; ++c) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const uint4 x = base[((i & 3) + 8 * (i >> 2)) * CPR + c];
-          uint32_t a = acc[i];
-          a = __builtin_amdgcn_sad_u8(x.x, q[4 * c + 0], a);
-          a = __builtin_amdgcn_sad_u8(x.y, q[4 * c + 1], a);
-          a = __builtin_amdgcn_sad_u8(x.z, q[4 * c + 2], a);
-          a = __builtin_amdgcn_sad_u8(x.w, q[4 * c + 3], a);
-          acc[i] = a;
-        }
+        for (int i = 0; i < 16; ++i)
+          acc[i] = code_sad4<SadU8>(base[code_row(i) * CPR + c], &q[4 * c], acc[i]);
       }
       // (the sums are below 2^24: exact floats; a pad row's seed makes it +inf)
       f32x16 av;
       const float* sr = &sx[cur][sub * kTR + 4 * h];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[(i & 3) + 8 * (i >> 2)];
+      for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[code_row(i)];
       select_block<R>(av, (t * (TR / kTR) + sub) * kTR, h, L, I, thr, tq);
     }
 
-    if (xch) {
-      // lanes l and l ^ 32 hold the two halves of the query's slots
-      const auto sw = __builtin_amdgcn_permlane32_swap(gmx, gmx, false, false);
-      tq = __builtin_fminf(tq, key2f(max(sw[0], sw[1])));
-    }
+    if (xch) tq = __builtin_fminf(tq, code_fetched(gmx));
     if (it + 1 < my_nt) store_tile(cur ^ 1);
     // the next tile is in LDS for every wave, and every wave is done reading
     // this one before tile it + 2 is stored over it
@@ -201,35 +149,14 @@ cand_sad_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   write_lists<R>(out_v, out_i, qg, S, split, h, L, I);
 }
 
-template <int DP, int R, int NW>
-static void launch_sad(const CandLaunch& c, hipStream_t s) {
-  const int nt = (int)(c.n_pad / sad_tile_rows_c(DP));
-  const dim3 grid((unsigned)(c.n_qt * c.S)), block(NW * 64);
-  if (c.ev_start)
-    hipExtLaunchKernelGGL((cand_sad_kernel<DP, R, NW>), grid, block, 0, s, c.ev_start, c.ev_stop, 0,
-                          (const uint4*)c.X32, (const uint4*)c.Q32, c.xinit, nt, c.S, c.n_qt,
-                          c.out_v, c.out_i, c.gthr, c.gk, c.gmask);
-  else
-    hipLaunchKernelGGL((cand_sad_kernel<DP, R, NW>), grid, block, 0, s, (const uint4*)c.X32,
-                       (const uint4*)c.Q32, c.xinit, nt, c.S, c.n_qt, c.out_v, c.out_i, c.gthr,
-                       c.gk, c.gmask);
-}
-
 // Instantiated: DP = pad_dim_i8w's values, R in {8, 16}, NW in {4, 8} -- what
 // the plan can ask for (knn_plan.cpp, resident_variant).
 #define KNN_SAD_DPS(X) X(32) X(64) X(96) X(128) X(160) X(192) X(256)
 
 template <class F>
 static bool sad_dispatch(int DP, int R, int nw, F f) {
-  if ((R != 8 && R != 16) || (nw != 4 && nw != 8)) return false;
-#define KNN_CASE(v)                                                              \
-  if (DP == v) {                                                                 \
-    if (R == 8 && nw == 4) f(std::integral_constant<int, v>{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 4>{});        \
-    else if (R == 8) f(std::integral_constant<int, v>{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{});             \
-    else if (nw == 4) f(std::integral_constant<int, v>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 4>{});           \
-    else f(std::integral_constant<int, v>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 8>{});                        \
-    return true;                                                                 \
-  }
+#define KNN_CASE(v) \
+  if (DP == v) return code_dispatch(R, nw, [&](auto r, auto w) { f(code_ic<v>{}, r, w); });
   KNN_SAD_DPS(KNN_CASE)
 #undef KNN_CASE
   return false;
@@ -239,7 +166,8 @@ bool launch_cand_sad(const CandLaunch& c, hipStream_t s) {
   // the host's query tile must be this kernel's: nw waves x 32 queries
   if (c.qpb != c.nw * 32 || !c.xinit) return false;
   return sad_dispatch(c.DP, c.R, c.nw, [&](auto dp, auto r, auto nw) {
-    launch_sad<dp.value, r.value, nw.value>(c, s);
+    launch_code_kernel(cand_sad_kernel<dp.value, r.value, nw.value>, c, s,
+                       (int)(c.n_pad / sad_tile_rows_c(dp.value)));
   });
 }
 

@@ -29,9 +29,7 @@
 // v_sad_u8 (one query dword per 16 v_sad_u8).  After the last chunk the
 // sums are converted and selected once (select_block).  DP is a run-time
 // argument: one instantiation per (R, NW).
-#include "knn_device.h"
-
-#include <hip/hip_ext.h>
+#include "knn_cand_codes.h"
 
 namespace knnk {
 
@@ -41,12 +39,6 @@ constexpr int kSadWideRows = kTR;   // rows per staged tile: one sub-tile
 // need (knn_select.hip, 64 | trows)
 constexpr int kSadWideSplitRows = 2 * kSadWideRows;
 constexpr int kSadWideMaxCPR = 64;  // 16-B steps per row at most (DP <= 1024)
-
-// (knn_cand_sad.hip's exchange schedule: early at 0, 1, 2, 4, then every 8th)
-__device__ __forceinline__ bool sadw_exchange_tile(int it) {
-  if (it < 8) return it == 0 || it == 1 || it == 2 || it == 4;
-  return (it & 7) == 7;
-}
 
 template <int R, int NW>
 __global__ void __launch_bounds__(NW * 64)
@@ -60,7 +52,7 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   constexpr int NPT = NCHMAX / NT;             // chunks per thread at most
   constexpr uint32_t FLIP = 0x80808080u;
   __shared__ uint4 lds[2][NCHMAX];
-  __shared__ float sx[2][TR];  // the tile's rows' seeds (xinit_l1: 0, +inf on pad rows)
+  __shared__ float sx[2][TR];  // the tile's rows' seeds
 
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int split = bid / n_qt, qt = bid - split * n_qt;
@@ -88,27 +80,11 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   const int my_nt = split < n_tiles ? 2 * ((n_tiles - split + S - 1) / S) : 0;
   auto tile_of = [&](int it) { return 2 * (split + (it >> 1) * S) + (it & 1); };
 
-  // staging: the image's rows are DP bytes, so a tile is nch contiguous
-  // chunks, kept in that order in LDS; this thread's are tid, tid + NT, ...
-  uint4 st[NPT];
-  float sxv = 0.0f;
+  // the image's rows are DP bytes, so a tile is nch contiguous chunks, kept
+  // in that order in LDS
+  CodeStage<NT, NPT, TR, FLIP, false> stg;
   auto load_tile = [&](int t) {
-    const uint4* g = X8 + (int64_t)t * nch;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int e = tid + u * NT;
-      if (e < nch) st[u] = g[e];
-    }
-    if (tid < TR) sxv = xinit[(int64_t)t * TR + tid];
-  };
-  auto store_tile = [&](int b) {
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-      const int e = tid + u * NT;
-      if (e < nch)
-        lds[b][e] = make_uint4(st[u].x ^ FLIP, st[u].y ^ FLIP, st[u].z ^ FLIP, st[u].w ^ FLIP);
-    }
-    if (tid < TR) sx[b][tid] = sxv;
+    stg.load(X8 + (int64_t)t * nch, xinit, t, tid, nch);
   };
   // steps c .. c + 3 of the query's codes (clamped to the row: a step past the
   // end is loaded again and not used)
@@ -119,44 +95,22 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
 
   if (my_nt > 0) {
     load_tile(tile_of(0));
-    store_tile(0);
+    stg.store(lds[0], sx[0], tid, nch);
   }
   __syncthreads();
 
   for (int it = 0; it < my_nt; ++it) {
     const int t = tile_of(it);
     const int cur = it & 1;
-    // the exchange, as in cand_sad_kernel: publish the lists' threshold and
-    // fetch the query's slots (read after the tile's compute)
-    const bool xch = gq && it + 1 < my_nt && sadw_exchange_tile(it);
+    const bool xch = gq && it + 1 < my_nt && code_exchange_tile(it);
     uint32_t gmx = 0;
-    if (xch) {
-      float mv;
-      if (gk) {
-        float u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = L[e];
-        mv = union_kth<2>(u, gk);
-      } else {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr), __float_as_uint(thr),
-                                                         false, false);
-        mv = __builtin_fminf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      }
-      const uint32_t pk = f2key(mv);
-      if (h == 0 && pk < last_pub) {
-        atomicMin(gq + (split & gmask), pk);
-        last_pub = pk;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        gmx = max(gmx, __hip_atomic_load(gq + 4 * h + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
+    if (xch) gmx = code_publish_fetch<R>(L, thr, last_pub, gq, gk, h, split, gmask);
     if (it + 1 < my_nt) load_tile(tile_of(it + 1));
 
     // this lane's 16 rows of the tile, advanced a chunk at a time
     const uint4* rp[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) rp[i] = &lds[cur][((i & 3) + 8 * (i >> 2) + 4 * h) * CPR];
+    for (int i = 0; i < 16; ++i) rp[i] = &lds[cur][(code_row(i) + 4 * h) * CPR];
     uint32_t acc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0;
@@ -178,15 +132,7 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
       for (int u = 0; u < 4; ++u) {
         if (u < ns) {
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const uint4 x = rp[i][u];
-            uint32_t a = acc[i];
-            a = __builtin_amdgcn_sad_u8(x.x, q[4 * u + 0], a);
-            a = __builtin_amdgcn_sad_u8(x.y, q[4 * u + 1], a);
-            a = __builtin_amdgcn_sad_u8(x.z, q[4 * u + 2], a);
-            a = __builtin_amdgcn_sad_u8(x.w, q[4 * u + 3], a);
-            acc[i] = a;
-          }
+          for (int i = 0; i < 16; ++i) acc[i] = code_sad4<SadU8>(rp[i][u], &q[4 * u], acc[i]);
         }
       }
 #pragma unroll
@@ -196,15 +142,11 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
     f32x16 av;
     const float* sr = &sx[cur][4 * h];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[(i & 3) + 8 * (i >> 2)];
+    for (int i = 0; i < 16; ++i) av[i] = (float)acc[i] + sr[code_row(i)];
     select_block<R>(av, t * TR, h, L, I, thr, tq);
 
-    if (xch) {
-      // lanes l and l ^ 32 hold the two halves of the query's slots
-      const auto sw = __builtin_amdgcn_permlane32_swap(gmx, gmx, false, false);
-      tq = __builtin_fminf(tq, key2f(max(sw[0], sw[1])));
-    }
-    if (it + 1 < my_nt) store_tile(cur ^ 1);
+    if (xch) tq = __builtin_fminf(tq, code_fetched(gmx));
+    if (it + 1 < my_nt) stg.store(lds[cur ^ 1], sx[cur ^ 1], tid, nch);
     // the next tile is in LDS for every wave, and every wave is done reading
     // this one before tile it + 2 is stored over it
     __syncthreads();
@@ -212,44 +154,20 @@ cand_sad_wide_kernel(const uint4* __restrict__ X8, const uint4* __restrict__ Q8,
   write_lists<R>(out_v, out_i, qg, S, split, h, L, I);
 }
 
-template <int R, int NW>
-static void launch_sadw(const CandLaunch& c, hipStream_t s) {
-  const int nt = (int)(c.n_pad / kSadWideSplitRows);
-  const int cpr = c.DP / 16;
-  const dim3 grid((unsigned)(c.n_qt * c.S)), block(NW * 64);
-  if (c.ev_start)
-    hipExtLaunchKernelGGL((cand_sad_wide_kernel<R, NW>), grid, block, 0, s, c.ev_start, c.ev_stop, 0,
-                          (const uint4*)c.X32, (const uint4*)c.Q32, c.xinit, cpr, nt, c.S, c.n_qt,
-                          c.out_v, c.out_i, c.gthr, c.gk, c.gmask);
-  else
-    hipLaunchKernelGGL((cand_sad_wide_kernel<R, NW>), grid, block, 0, s, (const uint4*)c.X32,
-                       (const uint4*)c.Q32, c.xinit, cpr, nt, c.S, c.n_qt, c.out_v, c.out_i, c.gthr,
-                       c.gk, c.gmask);
-}
-
-// Instantiated: R in {8, 16}, NW in {4, 8} -- what the plan can ask for
-// (knn_plan.cpp, resident_variant).
-template <class F>
-static bool sadw_dispatch(int R, int nw, F f) {
-  if ((R != 8 && R != 16) || (nw != 4 && nw != 8)) return false;
-  if (R == 8 && nw == 4) f(std::integral_constant<int, 8>{}, std::integral_constant<int, 4>{});
-  else if (R == 8) f(std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{});
-  else if (nw == 4) f(std::integral_constant<int, 16>{}, std::integral_constant<int, 4>{});
-  else f(std::integral_constant<int, 16>{}, std::integral_constant<int, 8>{});
-  return true;
-}
-
 bool sad_wide_dp(int DP) { return DP > 256 && DP <= 16 * kSadWideMaxCPR && DP % 16 == 0; }
 
 bool launch_cand_sad_wide(const CandLaunch& c, hipStream_t s) {
   // the host's query tile and train rows must be this kernel's
   if (!sad_wide_dp(c.DP) || c.qpb != c.nw * 32 || !c.xinit || c.n_pad % kSadWideSplitRows) return false;
-  return sadw_dispatch(c.R, c.nw, [&](auto r, auto nw) { launch_sadw<r.value, nw.value>(c, s); });
+  return code_dispatch(c.R, c.nw, [&](auto r, auto nw) {
+    launch_code_kernel(cand_sad_wide_kernel<r.value, nw.value>, c, s, c.DP / 16,
+                       (int)(c.n_pad / kSadWideSplitRows));
+  });
 }
 
 int sad_wide_blocks_per_cu(int R, int nw) {
   int out = 1;
-  sadw_dispatch(R, nw, [&](auto r, auto w) {
+  code_dispatch(R, nw, [&](auto r, auto w) {
     out = occupancy_of(cand_sad_wide_kernel<r.value, w.value>, w.value * 64);
   });
   return out;
