@@ -1041,6 +1041,61 @@ static int check_query_args(knn_ctx* ctx, int64_t m, int32_t k, int32_t metric) 
   return KNN_OK;
 }
 
+// ---- per-class evaluation (knn_eval.hip)
+// The sweep (under exclusion with d_excl) into d_labels or, without them, the
+// context's workspace, then the confusion pass over those labels.  zero: the
+// call clears d_conf / d_unl first, as the sweep clears d_correct; the
+// leave-one-out host twin sums its batches on the device without it.
+static int sweep_eval(knn_ctx* ctx, const double* dQ, int64_t m, const int64_t* d_excl,
+                      const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
+                      const int32_t* d_truth, int64_t* d_correct, int64_t* d_conf, int64_t* d_unl,
+                      bool zero, hipStream_t s) {
+  int rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
+  if (!d_truth)
+    return knn_fail(KNN_ERR_ARG, "null d_truth (the evaluation needs the queries' true labels)");
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  if (zero && d_conf) HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)nk * cc * sizeof(int64_t), s));
+  if (zero && d_unl) HIP_TRY(hipMemsetAsync(d_unl, 0, (size_t)nk * sizeof(int64_t), s));
+  int32_t* L = d_labels;
+  if (!L) {
+    const size_t cells = (size_t)std::max<int64_t>(m, 1) * nk;
+    if ((rc = ctx->ev_lab.ensure(cells * sizeof(int32_t)))) return rc;
+    L = (int32_t*)ctx->ev_lab.p;
+  }
+  rc = knn_classify_sweep_excl_device(ctx, dQ, m, d_excl, ks, nk, metric, L,
+                                      d_correct ? d_truth : nullptr, d_correct, nullptr, nullptr,
+                                      nullptr, s);
+  if (rc || m == 0 || (!d_conf && !d_unl)) return rc;
+  launch_eval_confusion(L, nk, m, d_truth, ctx->class_cnt, (unsigned long long*)d_conf,
+                        (unsigned long long*)d_unl, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the confusion pass
+  return KNN_OK;
+}
+
+// leave-one-out over train rows [row0, row0 + rows): the rows are the queries,
+// each excludes itself and its own label is its truth
+int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                      int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_conf,
+                      int64_t* d_unl, bool zero, hipStream_t s) {
+  int rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-one-out sweep before set_train");
+  const TrainDev& t = ctx->train;
+  if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
+    return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
+                                     std::to_string(row0) + " + " + std::to_string(rows) +
+                                     ") outside the train set [0, " + std::to_string(t.n) + ")");
+  if ((rc = ctx->loo_excl.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int64_t)))) return rc;
+  int64_t* excl = (int64_t*)ctx->loo_excl.p;
+  launch_loo_self(excl, rows, ctx->idx_off + row0, s);
+  HIP_TRY(hipGetLastError());
+  return sweep_eval(ctx, t.X64 + row0 * t.d, rows, excl, ks, nk, metric, d_labels, t.lab + row0,
+                    d_correct, d_conf, d_unl, zero, s);
+}
+
 extern "C" {
 
 int knn_classify_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t k, int32_t metric,
@@ -1387,6 +1442,173 @@ int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, i
       HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
                              (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
   }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_correct)
+    for (int32_t j = 0; j < nk; j++) {
+      out_correct[j] = 0;
+      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
+    }
+  return KNN_OK;
+}
+
+// ---- per-class evaluation (knn_eval.hip): the confusion matrix at every K
+// of a sweep, the vote counts of ordered neighbour rows
+
+int knn_confusion_device(knn_ctx* ctx, const int32_t* d_labels, int32_t nk, int64_t m,
+                         const int32_t* d_truth, int32_t class_cnt, int64_t* d_conf,
+                         int64_t* d_unl, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (nk < 1 || nk > 4096)
+    return knn_fail(KNN_ERR_ARG, "nk = " + std::to_string(nk) + " must be in [1, 4096]");
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
+  if (!d_conf) return knn_fail(KNN_ERR_ARG, "null d_conf");
+  if (m == 0) return KNN_OK;
+  if (!d_truth) return knn_fail(KNN_ERR_ARG, "null d_truth");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null d_labels");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  launch_eval_confusion(d_labels, nk, m, d_truth, class_cnt, (unsigned long long*)d_conf,
+                        (unsigned long long*)d_unl, s);
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+int knn_vote_counts_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_t kmax,
+                           const int32_t* d_lab, int64_t idx_base, int32_t k, int32_t class_cnt,
+                           int32_t* d_counts, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  if (k < 0) return knn_fail(KNN_ERR_ARG, "k must be >= 0");
+  if (k > kmax)
+    return knn_fail(KNN_ERR_ARG, "k = " + std::to_string(k) + " exceeds kmax = " +
+                                     std::to_string(kmax) + " (the entries of a row)");
+  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
+  if (!d_counts) return knn_fail(KNN_ERR_ARG, "null d_counts");
+  if (m == 0) return KNN_OK;
+  if (k > 0 && (!d_idx || !d_lab)) return knn_fail(KNN_ERR_ARG, "null neighbour rows / labels");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  HIP_TRY(launch_eval_vote_counts(d_idx, m, kmax, d_lab, idx_base, k, class_cnt, d_counts,
+                                  ctx->cu_count, s));
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+int knn_classify_sweep_eval_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                   const int64_t* d_excl, const int32_t* ks, int32_t nk,
+                                   int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                   int64_t* d_correct, int64_t* d_conf, int64_t* d_unl,
+                                   void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return sweep_eval(ctx, dQ, m, d_excl, ks, nk, metric, d_labels, d_truth, d_correct, d_conf,
+                    d_unl, true, s);
+}
+
+int knn_loo_sweep_eval_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks,
+                              int32_t nk, int32_t metric, int32_t* d_labels, int64_t* d_correct,
+                              int64_t* d_conf, int64_t* d_unl, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return knn_loo_eval_rows(ctx, row0, rows, ks, nk, metric, d_labels, d_correct, d_conf, d_unl,
+                           true, s);
+}
+
+int knn_classify_sweep_eval(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks,
+                            int32_t nk, int32_t metric, int32_t* out_labels, const int32_t* truth,
+                            int64_t* out_correct, int64_t* out_conf, int64_t* out_unl) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
+  if (!truth) return knn_fail(KNN_ERR_ARG, "null truth (the evaluation needs the true labels)");
+  if (m > 0 && !Q) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const int d = ctx->train.d;
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  const size_t m1 = (size_t)std::max<int64_t>(m, 1);
+  if ((rc = ctx->Q64.ensure(m1 * d * sizeof(double)))) return rc;
+  if ((rc = ctx->sw_truth.ensure(m1 * sizeof(int32_t)))) return rc;
+  if (out_labels && (rc = ctx->sw_out.ensure(m1 * nk * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (m > 0) {
+    HIP_TRY(hipMemcpyAsync(ctx->Q64.p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->sw_truth.p, truth, (size_t)m * sizeof(int32_t),
+                           hipMemcpyHostToDevice, s));
+  }
+  rc = sweep_eval(ctx, (const double*)ctx->Q64.p, m, nullptr, ks, nk, metric,
+                  out_labels ? (int32_t*)ctx->sw_out.p : nullptr, (const int32_t*)ctx->sw_truth.p,
+                  out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
+                  out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
+                  out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, true, s);
+  if (rc) return rc;
+  if (out_labels && m > 0)
+    HIP_TRY(hipMemcpyAsync(out_labels, ctx->sw_out.p, (size_t)m * nk * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_correct)
+    HIP_TRY(hipMemcpyAsync(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_conf)
+    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_unl)
+    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return KNN_OK;
+}
+
+int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric,
+                       int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                       int64_t* out_unl) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
+  const int64_t n = ctx->train.n;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
+  // fixed batches: the workspace does not grow with n -- without out_labels no
+  // [nk][n] array exists anywhere
+  const int64_t B = std::min<int64_t>(n, 16384);
+  const int64_t nb = (n + B - 1) / B;
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  hipStream_t s = ctx->stream;
+  // conf / unl are summed over the batches on the device, correct on the host
+  if (out_conf) HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+  if (out_unl) HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
+  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t r0 = b * B, rows = std::min(B, n - r0);
+    rc = knn_loo_eval_rows(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
+                  out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
+                  out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
+                  out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, false, s);
+    if (rc) return rc;
+    if (out_labels)
+      HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
+                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                               (size_t)nk, hipMemcpyDeviceToHost, s));
+    if (out_correct)
+      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, s));
+  }
+  if (out_conf)
+    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_unl)
+    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (out_correct)
     for (int32_t j = 0; j < nk; j++) {

@@ -109,6 +109,9 @@ struct knn_ctx {
   // K sweep under exclusion: the search's rows / flags at kmax + 1, the
   // exclusions of a leave-one-out batch (and the host twin's staging)
   DevBuf loo_idx, loo_dist, loo_flags, loo_excl;
+  // per-class evaluation: the sweep's labels [nk][m] when the caller wants
+  // none, host-API staging of conf [nk][C][C] and unl [nk]
+  DevBuf ev_lab, ev_conf, ev_unl;
   // host-API outputs
   DevBuf o_lab, o_idx, o_dist, o_flags;
   // normalisation: per-thread partial max/min, bounds, host-API staging
@@ -121,7 +124,8 @@ struct knn_ctx {
             &rescan_mask, &rescan_nkeep, &rescan_qc8, &rescan_t8, &smp_x64, &smp_xl2, &smp_img, &smp_scr, &smp_v, &smp_i,
             &ord_cent, &ord_cnorm, &ord_img, &ord_rank, &ord_rstart, &ord_perm, &ord_ipos, &ord_key, &ord_bcnt, &ord_tot,
             &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
-            &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl};
+            &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl,
+            &ev_lab, &ev_conf, &ev_unl};
   }
 };
 
@@ -129,5 +133,11 @@ int knn_fail(int code, const std::string& msg);
 // K sweep argument check shared with knn_group.cpp: 1 <= nk <= 4096 and 0 <=
 // ks[i] <= n (KNN_ERR_ARG naming the offending entry); *kmax = max K
 int knn_sweep_check_ks(const int32_t* ks, int32_t nk, int64_t n, int32_t* kmax);
+// Leave-one-out sweep with evaluation over train rows [row0, row0 + rows)
+// (knn_loo_sweep_eval_device's body): zero = false ADDS into d_conf / d_unl,
+// so the callers that walk the train set in batches sum them on the device
+int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                      int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_conf,
+                      int64_t* d_unl, bool zero, hipStream_t s);
 int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                    const knnk::Sink& sink, hipStream_t s);

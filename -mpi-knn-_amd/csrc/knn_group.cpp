@@ -50,6 +50,7 @@ struct knn_group {
   std::vector<DevBuf> pk, gk;                  // train-sharded packed partial / gathered lists
   std::vector<DevBuf> tq, tcnt, tsel, trow, tsend, trecv;  // reference tie order exchange
   std::vector<DevBuf> slab, struth, scorr, sks;  // K sweep: labels [nk][mi], truth, correct counts, ks
+  std::vector<DevBuf> sconf, sunl;             // per-class evaluation: conf [nk][C][C], unl [nk]
   std::vector<DevBuf> nX, nmm;                 // normalisation shards / per-dim bounds
   std::vector<hipEvent_t> ev0, ev1;            // per device: around the last call's device work
   std::vector<hipEvent_t> evx;                 // loopback: cross-rank stream ordering
@@ -344,7 +345,8 @@ int knn_group_create(knn_group** out, int ndev, const int* devs, int mode) {
   }
   for (auto* v : {&g->X, &g->lab, &g->labA, &g->Q, &g->olab, &g->oidx, &g->odist, &g->oflags,
                   &g->pk, &g->gk, &g->tq, &g->tcnt, &g->tsel, &g->trow, &g->tsend, &g->trecv,
-                  &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks})
+                  &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks,
+                  &g->sconf, &g->sunl})
     v->resize(ndev);
   g->ev0.assign(ndev, nullptr);
   g->ev1.assign(ndev, nullptr);
@@ -390,7 +392,8 @@ int knn_group_destroy(knn_group* g) {
     }
     for (auto* v : {&g->X, &g->lab, &g->labA, &g->Q, &g->olab, &g->oidx, &g->odist, &g->oflags,
                     &g->pk, &g->gk, &g->tq, &g->tcnt, &g->tsel, &g->trow, &g->tsend, &g->trecv,
-                    &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks})
+                    &g->nX, &g->nmm, &g->slab, &g->struth, &g->scorr, &g->sks,
+                  &g->sconf, &g->sunl})
       if (i < (int)v->size()) (*v)[i].release();
     for (auto* ev : {&g->ev0, &g->ev1, &g->evx})
       if (i < (int)ev->size() && (*ev)[i]) (void)hipEventDestroy((*ev)[i]);
@@ -776,21 +779,30 @@ int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int3
   return finish();
 }
 
-int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
-                             int32_t nk, int32_t metric, int32_t* out_labels,
-                             const int32_t* truth, int64_t* out_correct) {
+// eval: the per-class evaluation rides along (knn_group_classify_sweep_eval):
+// truth is required, out_labels / out_correct / out_conf / out_unl are each
+// nullable, every rank counts conf / unl of its slice and the host sums them
+static int group_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks, int32_t nk,
+                       int32_t metric, int32_t* out_labels, const int32_t* truth,
+                       int64_t* out_correct, int64_t* out_conf, int64_t* out_unl, bool eval) {
   if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group classify sweep before set_train");
-  if (m < 0 || !out_labels || (m > 0 && !Q)) return knn_fail(KNN_ERR_ARG, "bad classify arguments");
+  if (m < 0 || (!eval && !out_labels) || (m > 0 && !Q))
+    return knn_fail(KNN_ERR_ARG, "bad classify arguments");
   if (m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be < 2^31 per call");
   if (metric != KNN_METRIC_L2 && metric != KNN_METRIC_L1)
     return knn_fail(KNN_ERR_ARG, "metric must be 0 (L2) or 1 (L1)");
   int rc;
   int32_t kmax = 0;
   if ((rc = knn_sweep_check_ks(ks, nk, g->n, &kmax))) return rc;
-  if ((truth != nullptr) != (out_correct != nullptr))
+  if (!eval && (truth != nullptr) != (out_correct != nullptr))
     return knn_fail(KNN_ERR_ARG, "truth and out_correct go together (both or neither)");
+  if (eval && !truth)
+    return knn_fail(KNN_ERR_ARG, "null truth (the evaluation needs the true labels)");
+  const size_t cc = (size_t)g->class_cnt * g->class_cnt;
   if (out_correct)
     for (int j = 0; j < nk; j++) out_correct[j] = 0;
+  if (out_conf) std::fill(out_conf, out_conf + (size_t)nk * cc, (int64_t)0);
+  if (out_unl) std::fill(out_unl, out_unl + nk, (int64_t)0);
   g->last_ties = 0;
   if (m == 0) return KNN_OK;
   const int G = g->ndev;
@@ -800,7 +812,9 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
     mi = m * (i + 1) / G - q0;
   };
   if (g->mode == 1 && kmax == 0) {  // every K is 0 (cpp:324: max_label stays -1)
-    for (int64_t e = 0; e < (int64_t)nk * m; e++) out_labels[e] = -1;
+    if (out_labels)
+      for (int64_t e = 0; e < (int64_t)nk * m; e++) out_labels[e] = -1;
+    if (out_unl) std::fill(out_unl, out_unl + nk, m);  // no query has a label
     return KNN_OK;
   }
   for (int i = 0; i < G; i++) {
@@ -812,17 +826,28 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
     if ((rc = g->struth[i].ensure(mi1 * sizeof(int32_t)))) return rc;
     if ((rc = g->scorr[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
     if (g->mode == 0 && (rc = g->Q[i].ensure(mi1 * d * sizeof(double)))) return rc;
+    if (eval && (rc = g->sconf[i].ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+    if (eval && (rc = g->sunl[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
   }
   // rank i's labels [nk][mi] -> columns [q0, q0 + mi) of the host's [nk][m];
   // its correct counts are summed on the host once the devices are done
-  std::vector<std::vector<int64_t>> hc(G, std::vector<int64_t>(truth ? nk : 0, 0));
+  std::vector<std::vector<int64_t>> hc(G, std::vector<int64_t>(out_correct ? nk : 0, 0));
+  std::vector<std::vector<int64_t>> hconf(G, std::vector<int64_t>(out_conf ? nk * cc : 0, 0));
+  std::vector<std::vector<int64_t>> hunl(G, std::vector<int64_t>(out_unl ? nk : 0, 0));
   auto d2h = [&](int i, int64_t q0, int64_t mi) -> int {
     hipStream_t s = g->ctx[i]->stream;
-    HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)m * sizeof(int32_t), g->slab[i].p,
-                           (size_t)mi * sizeof(int32_t), (size_t)mi * sizeof(int32_t), (size_t)nk,
-                           hipMemcpyDeviceToHost, s));
-    if (truth)
+    if (out_labels)
+      HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)m * sizeof(int32_t), g->slab[i].p,
+                             (size_t)mi * sizeof(int32_t), (size_t)mi * sizeof(int32_t),
+                             (size_t)nk, hipMemcpyDeviceToHost, s));
+    if (out_correct)
       HIP_G(hipMemcpyAsync(hc[i].data(), g->scorr[i].p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    if (out_conf)
+      HIP_G(hipMemcpyAsync(hconf[i].data(), g->sconf[i].p, (size_t)nk * cc * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    if (out_unl)
+      HIP_G(hipMemcpyAsync(hunl[i].data(), g->sunl[i].p, (size_t)nk * sizeof(int64_t),
                            hipMemcpyDeviceToHost, s));
     return KNN_OK;
   };
@@ -836,9 +861,11 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
         span = std::max(span, (double)ms * 1e-3);
     }
     g->last_compute = span;
-    if (truth)
-      for (int i = 0; i < G; i++)
-        for (int j = 0; j < nk; j++) out_correct[j] += hc[i][j];
+    for (int i = 0; i < G; i++) {
+      for (size_t j = 0; j < hc[i].size(); j++) out_correct[j] += hc[i][j];
+      for (size_t j = 0; j < hconf[i].size(); j++) out_conf[j] += hconf[i][j];
+      for (size_t j = 0; j < hunl[i].size(); j++) out_unl[j] += hunl[i][j];
+    }
     return KNN_OK;
   };
   if (g->mode == 0) {
@@ -858,12 +885,19 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
         HIP_G(hipMemcpyAsync(g->struth[i].p, truth + q0, (size_t)mi * sizeof(int32_t),
                              hipMemcpyHostToDevice, s));
       HIP_G(hipEventRecord(g->ev0[i], s));
-      if ((rc = knn_classify_sweep_device(g->ctx[i], (const double*)g->Q[i].p, mi, ks, nk, metric,
-                                          (int32_t*)g->slab[i].p,
-                                          truth ? (const int32_t*)g->struth[i].p : nullptr,
-                                          truth ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
-                                          nullptr, nullptr, s)))
-        return rc;
+      if (eval)
+        rc = knn_classify_sweep_eval_device(g->ctx[i], (const double*)g->Q[i].p, mi, nullptr, ks,
+                                            nk, metric, (int32_t*)g->slab[i].p,
+                                            (const int32_t*)g->struth[i].p,
+                                            out_correct ? (int64_t*)g->scorr[i].p : nullptr,
+                                            (int64_t*)g->sconf[i].p, (int64_t*)g->sunl[i].p, s);
+      else
+        rc = knn_classify_sweep_device(g->ctx[i], (const double*)g->Q[i].p, mi, ks, nk, metric,
+                                       (int32_t*)g->slab[i].p,
+                                       truth ? (const int32_t*)g->struth[i].p : nullptr,
+                                       truth ? (int64_t*)g->scorr[i].p : nullptr, nullptr, nullptr,
+                                       nullptr, s);
+      if (rc) return rc;
       HIP_G(hipEventRecord(g->ev1[i], s));
     }
     for (int i = 0; i < G; i++) {
@@ -908,9 +942,17 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
       if ((rc = knn_vote_sweep_device(g->ctx[i], (const int64_t*)g->oidx[i].p, mi, kmax,
                                       (const int32_t*)g->labA[i].p, 0, ks, nk,
                                       (int32_t*)g->slab[i].p,
-                                      truth ? (const int32_t*)g->struth[i].p : nullptr,
-                                      truth ? (int64_t*)g->scorr[i].p : nullptr, s)))
+                                      out_correct ? (const int32_t*)g->struth[i].p : nullptr,
+                                      out_correct ? (int64_t*)g->scorr[i].p : nullptr, s)))
         return rc;
+      if (eval) {  // the rank's slice of the labels against its slice of the truth
+        HIP_G(hipMemsetAsync(g->sconf[i].p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+        HIP_G(hipMemsetAsync(g->sunl[i].p, 0, (size_t)nk * sizeof(int64_t), s));
+        if ((rc = knn_confusion_device(g->ctx[i], (const int32_t*)g->slab[i].p, nk, mi,
+                                       (const int32_t*)g->struth[i].p, g->class_cnt,
+                                       (int64_t*)g->sconf[i].p, (int64_t*)g->sunl[i].p, s)))
+          return rc;
+      }
     }
     HIP_G(hipEventRecord(g->ev1[i], s));
   }
@@ -923,22 +965,42 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
   return finish();
 }
 
+int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
+                             int32_t nk, int32_t metric, int32_t* out_labels,
+                             const int32_t* truth, int64_t* out_correct) {
+  return group_sweep(g, Q, m, ks, nk, metric, out_labels, truth, out_correct, nullptr, nullptr,
+                     false);
+}
+
+int knn_group_classify_sweep_eval(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
+                                  int32_t nk, int32_t metric, int32_t* out_labels,
+                                  const int32_t* truth, int64_t* out_correct, int64_t* out_conf,
+                                  int64_t* out_unl) {
+  return group_sweep(g, Q, m, ks, nk, metric, out_labels, truth, out_correct, out_conf, out_unl,
+                     true);
+}
+
 // Leave-one-out K sweep (knn_loo.hip): in mode 0 every rank holds the whole
 // train set, so rank r sweeps train rows [n r / G, n (r + 1) / G) of its own
-// copy in batches of at most 16384 rows (fixed workspace).
-int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
-                        int32_t* out_labels, int64_t* out_correct) {
+// copy in batches of at most 16384 rows (fixed workspace).  eval: with the
+// per-class evaluation (knn_group_loo_sweep_eval; out_labels nullable): each
+// rank sums conf / unl over its batches on its GPU, the host over the ranks.
+static int group_loo(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                     int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                     int64_t* out_unl, bool eval) {
   if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group leave-one-out sweep before set_train");
   if (g->mode == 1)
     return knn_fail(KNN_ERR_ARG,
                     "the leave-one-out sweep is not served in the train-sharded mode (mode 1): "
                     "use a query-sharded group (mode 0)");
-  if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  if (!eval && !out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
   if (metric != KNN_METRIC_L2 && metric != KNN_METRIC_L1)
     return knn_fail(KNN_ERR_ARG, "metric must be 0 (L2) or 1 (L1)");
   int rc;
   int32_t kmax = 0;
   const int64_t n = g->n;
+  const size_t cc = (size_t)g->class_cnt * g->class_cnt;
+  std::vector<std::vector<int64_t>> hconf(g->ndev), hunl(g->ndev);
   if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
   const int G = g->ndev;
   const int64_t B = 16384;
@@ -956,18 +1018,40 @@ int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t met
       if ((rc = g->slab[i].ensure(bm * nk * sizeof(int32_t)))) return rc;
       if ((rc = g->scorr[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
     }
+    if (eval && nb > 0) {
+      if ((rc = g->sconf[i].ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+      if ((rc = g->sunl[i].ensure((size_t)nk * sizeof(int64_t)))) return rc;
+      HIP_G(hipMemsetAsync(g->sconf[i].p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+      HIP_G(hipMemsetAsync(g->sunl[i].p, 0, (size_t)nk * sizeof(int64_t), s));
+    }
     for (int64_t b = 0; b < nb; b++) {
       const int64_t q0 = r0 + b * B, rows = std::min(B, r1 - q0);
-      if ((rc = knn_loo_sweep_device(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
-                                     out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
-                                     nullptr, nullptr, s)))
-        return rc;
-      HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)n * sizeof(int32_t), g->slab[i].p,
-                             (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
-                             (size_t)nk, hipMemcpyDeviceToHost, s));
+      if (eval)
+        rc = knn_loo_eval_rows(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
+                               out_correct ? (int64_t*)g->scorr[i].p : nullptr,
+                               (int64_t*)g->sconf[i].p, (int64_t*)g->sunl[i].p, false, s);
+      else
+        rc = knn_loo_sweep_device(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
+                                  out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
+                                  nullptr, nullptr, s);
+      if (rc) return rc;
+      if (out_labels)
+        HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)n * sizeof(int32_t), g->slab[i].p,
+                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                               (size_t)nk, hipMemcpyDeviceToHost, s));
       if (out_correct)
         HIP_G(hipMemcpyAsync(hc[i].data() + b * nk, g->scorr[i].p, (size_t)nk * sizeof(int64_t),
                              hipMemcpyDeviceToHost, s));
+    }
+    if (eval && nb > 0 && out_conf) {
+      hconf[i].assign((size_t)nk * cc, 0);
+      HIP_G(hipMemcpyAsync(hconf[i].data(), g->sconf[i].p, (size_t)nk * cc * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    }
+    if (eval && nb > 0 && out_unl) {
+      hunl[i].assign((size_t)nk, 0);
+      HIP_G(hipMemcpyAsync(hunl[i].data(), g->sunl[i].p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
     }
     HIP_G(hipEventRecord(g->ev1[i], s));
   }
@@ -987,7 +1071,24 @@ int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t met
       for (int i = 0; i < G; i++)
         for (size_t b = 0; b * nk < hc[i].size(); b++) out_correct[j] += hc[i][b * nk + j];
     }
+  if (out_conf) std::fill(out_conf, out_conf + (size_t)nk * cc, (int64_t)0);
+  if (out_unl) std::fill(out_unl, out_unl + nk, (int64_t)0);
+  for (int i = 0; i < G; i++) {
+    for (size_t j = 0; j < hconf[i].size(); j++) out_conf[j] += hconf[i][j];
+    for (size_t j = 0; j < hunl[i].size(); j++) out_unl[j] += hunl[i][j];
+  }
   return KNN_OK;
+}
+
+int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                        int32_t* out_labels, int64_t* out_correct) {
+  return group_loo(g, ks, nk, metric, out_labels, out_correct, nullptr, nullptr, false);
+}
+
+int knn_group_loo_sweep_eval(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                             int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                             int64_t* out_unl) {
+  return group_loo(g, ks, nk, metric, out_labels, out_correct, out_conf, out_unl, true);
 }
 
 double knn_group_last_compute_seconds(knn_group* g) { return g ? g->last_compute : -1.0; }

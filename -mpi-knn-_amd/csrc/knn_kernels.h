@@ -418,6 +418,27 @@ void launch_sweep_tie_scan(const double* dist, const int64_t* idx, const int32_t
 void launch_sweep_vote(const int64_t* idx, int64_t m, int kmax, const int32_t* lab,
                        int64_t idx_base, const int* ks, int nk, int32_t* labels,
                        const int32_t* truth, unsigned long long* correct, int cus, hipStream_t s);
+// Per-class evaluation (knn_eval.hip).
+// confusion: conf[i][t][p] (nk x C x C, 64-bit) += #{q : truth[q] == t and
+// labels[i][q] == p} over labels [nk][m]; unl[i] += #{q : labels[i][q] or
+// truth[q] outside [0, C)}.  Both ADD (zeroed by the caller) and each is
+// nullable.  The histograms live in LDS by class_cnt: per-wave copies up to
+// kEvalSmallC, one per workgroup up to kEvalLdsC, global atomics beyond
+// (eval_confusion_regime: 0 / 1 / 2).
+constexpr int kEvalSmallC = 16;
+constexpr int kEvalLdsC = 96;
+int eval_confusion_regime(int class_cnt);
+void launch_eval_confusion(const int32_t* labels, int nk, int64_t m, const int32_t* truth,
+                           int class_cnt, unsigned long long* conf, unsigned long long* unl,
+                           hipStream_t s);
+// vote counts: counts[q][c] (m x C, int32) = #{t < k : lab[idx[q][t] - idx_base]
+// == c} over ordered rows idx [m][kmax] (k <= kmax; idx -1: an empty slot,
+// counted nowhere).  Per-wave LDS counters up to kEvalCountsLdsC classes;
+// beyond, the rows are zeroed on the stream and counted with global atomics.
+constexpr int kEvalCountsLdsC = 1024;
+hipError_t launch_eval_vote_counts(const int64_t* idx, int64_t m, int kmax, const int32_t* lab,
+                                   int64_t idx_base, int k, int class_cnt, int32_t* counts,
+                                   int cus, hipStream_t s);
 // fp64 rows -> [hi(DP) | lo(DP)] bf16 rows of scale*x (candidate metric 2 = L2 via bf16x3)
 // rows of `out` are row_shorts 16-bit words; xl2/xl1 (train only, else null)
 // fill the padded row's seed floats after the 2*DP bf16 payload

@@ -27,6 +27,12 @@
 // replaced by a leave-one-out sweep of the train set (knn_group_loo_sweep:
 // every train row classified against all the others), prints "K = <k> loo
 // accuracy = <acc>" per K, selects K the same way and runs the test pass.
+// --confusion (with the default validation pass, --K_list or --loo): after that
+// pass's lines prints "confusion K = <k>" for the selected K, then class_cnt
+// lines of class_cnt space-separated counts (row = true class, column =
+// predicted class) and "unlabelled = <n>" (queries whose label or truth is
+// outside [0, class_cnt)), from knn_group_classify_sweep_eval /
+// knn_group_loo_sweep_eval; without the flag stdout is unchanged.
 // The timed region spans the same work as the reference (barrier to
 // barrier: CSV parsing, distribution, normalisation, both passes, output).
 #include <chrono>
@@ -63,6 +69,7 @@ struct Config {
   bool timings = false;
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
+  bool confusion = false;       // --confusion: print the selected K's confusion matrix
   std::vector<std::pair<std::string, long long>> tune;  // --tune KEY=VALUE (knn_set_tuning keys)
 };
 
@@ -74,11 +81,14 @@ void usage() {
           "  [--class_cnt C] [--Euclidean_distance true|false] [--Normalize true|false]\n"
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
-          "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--tune KEY=VALUE]...\n"
+          "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--confusion]\n"
+          "  [--tune KEY=VALUE]...\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
           "  (no validation file is read)\n"
+          "  --confusion prints the confusion matrix of the validation (or --loo) pass at the\n"
+          "  selected K: class_cnt rows (true class) of class_cnt counts (predicted class)\n"
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
           "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
           "  (i8l1=2: also at 256 < dim <= 1024); --tune u16l1=1: the L1 pass on 16-bit\n"
@@ -115,6 +125,7 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "strict") { c.strict = true; continue; }
     else if (a == "timings") { c.timings = true; continue; }
     else if (a == "loo") { c.loo = true; continue; }
+    else if (a == "confusion") { c.confusion = true; continue; }
     else if (i + 1 < argc) v = argv[++i];
     else { usage(); return 1; }
     if (a == "dim") c.dim = atoi(v.c_str());
@@ -135,6 +146,7 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "strict") c.strict = parse_bool(v);
     else if (a == "threads") c.threads = atoi(v.c_str());
     else if (a == "loo") c.loo = parse_bool(v);
+    else if (a == "confusion") c.confusion = parse_bool(v);
     else if (a == "K_list") {
       if (!parse_k_list(v, c.K_list)) {
         fprintf(stderr, "--K_list takes a comma-separated list of non-negative integers\n");
@@ -171,6 +183,17 @@ void load(const std::string& path, int dim, bool with_label, int64_t rows, std::
   const int64_t want = rows * (dim + (with_label ? 1 : 0));
   if (r.tokens != want)
     die(path + ": expected " + std::to_string(want) + " values, found " + std::to_string(r.tokens));
+}
+
+// "confusion K = <k>", the C x C matrix of list entry `sel` (conf: [nk][C][C]),
+// "unlabelled = <n>"
+void print_confusion(int32_t k, int C, const int64_t* conf, int64_t unl) {
+  std::cout << "confusion K = " << k << std::endl;
+  for (int t = 0; t < C; t++) {
+    for (int p = 0; p < C; p++) std::cout << (p ? " " : "") << conf[(size_t)t * C + p];
+    std::cout << std::endl;
+  }
+  std::cout << "unlabelled = " << unl << std::endl;
 }
 
 }  // namespace
@@ -237,14 +260,20 @@ int main(int argc, char** argv) {
     die(knn_last_error());
   phase("set_train");
   const int metric = c.Euclidean_distance ? KNN_METRIC_L2 : KNN_METRIC_L1;
+  const size_t cc = (size_t)c.class_cnt * c.class_cnt;
 
   if (c.loo) {  // cpp:308-349 with every train row judged against all the others
     const int32_t nk = (int32_t)c.K_list.size();
     std::vector<int32_t> pred((size_t)nk * c.N_train);
     std::vector<int64_t> correct(nk, 0);
-    if (knn_group_loo_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data()))
+    std::vector<int64_t> conf(c.confusion ? nk * cc : 0, 0), unl(c.confusion ? nk : 0, 0);
+    if (c.confusion
+            ? knn_group_loo_sweep_eval(g, c.K_list.data(), nk, metric, pred.data(), correct.data(),
+                                       conf.data(), unl.data())
+            : knn_group_loo_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data()))
       die(knn_last_error());
     double best = -1.0;
+    int32_t sel = 0;
     for (int32_t i = 0; i < nk; i++) {
       double acc = (double)correct[i];  // acc_calc, cpp:69-84
       acc /= c.N_train;
@@ -252,18 +281,26 @@ int main(int argc, char** argv) {
       if (acc > best) {  // first to strictly exceed, like cpp:332-335
         best = acc;
         c.K = c.K_list[i];
+        sel = i;
       }
     }
     std::cout << "selected K = " << c.K << std::endl;
+    if (c.confusion) print_confusion(c.K, c.class_cnt, conf.data() + sel * cc, unl[sel]);
     phase("loo");
   } else if (!c.K_list.empty()) {  // the validation pass (cpp:308-349) for every K of the list
     const int32_t nk = (int32_t)c.K_list.size();
     std::vector<int32_t> pred((size_t)nk * c.N_val);
     std::vector<int64_t> correct(nk, 0);
-    if (knn_group_classify_sweep(g, Xva.data(), c.N_val, c.K_list.data(), nk, metric, pred.data(),
-                                 Lva.data(), correct.data()))
+    std::vector<int64_t> conf(c.confusion ? nk * cc : 0, 0), unl(c.confusion ? nk : 0, 0);
+    if (c.confusion
+            ? knn_group_classify_sweep_eval(g, Xva.data(), c.N_val, c.K_list.data(), nk, metric,
+                                            pred.data(), Lva.data(), correct.data(), conf.data(),
+                                            unl.data())
+            : knn_group_classify_sweep(g, Xva.data(), c.N_val, c.K_list.data(), nk, metric,
+                                       pred.data(), Lva.data(), correct.data()))
       die(knn_last_error());
     double best = -1.0, best_acc = 0.0;
+    int32_t sel = 0;
     for (int32_t i = 0; i < nk; i++) {
       double acc = (double)correct[i];  // acc_calc, cpp:69-84
       acc /= c.N_val;
@@ -272,10 +309,12 @@ int main(int argc, char** argv) {
         best = acc;
         best_acc = acc;
         c.K = c.K_list[i];
+        sel = i;
       }
     }
     std::cout << "selected K = " << c.K << std::endl;
     std::cout << "accuracy = " << best_acc << std::endl;
+    if (c.confusion) print_confusion(c.K, c.class_cnt, conf.data() + sel * cc, unl[sel]);
     phase("validation");
   } else if (c.Validation) {  // cpp:308-349
     std::vector<int32_t> pred(c.N_val);
@@ -287,6 +326,15 @@ int main(int argc, char** argv) {
       if (Lva[i] == pred[i]) acc++;
     acc /= c.N_val;
     std::cout << "accuracy = " << acc << std::endl;
+    if (c.confusion && c.N_val > 0) {  // the same pass as a one-K sweep, for its matrix
+      const int32_t k1 = c.K;
+      std::vector<int64_t> conf(cc, 0);
+      int64_t unl = 0;
+      if (knn_group_classify_sweep_eval(g, Xva.data(), c.N_val, &k1, 1, metric, nullptr, Lva.data(),
+                                        nullptr, conf.data(), &unl))
+        die(knn_last_error());
+      print_confusion(c.K, c.class_cnt, conf.data(), unl);
+    }
     phase("validation");
   }
 

@@ -42,7 +42,14 @@ EXPORTED = (
     "knn_vote_sweep_device", "knn_classify_sweep_device", "knn_classify_sweep",
     "knn_group_classify_sweep", "knn_classify_sweep_excl_device", "knn_loo_sweep_device",
     "knn_loo_sweep", "knn_group_loo_sweep",
+    "knn_confusion_device", "knn_vote_counts_device", "knn_classify_sweep_eval_device",
+    "knn_loo_sweep_eval_device", "knn_classify_sweep_eval", "knn_loo_sweep_eval",
+    "knn_group_classify_sweep_eval", "knn_group_loo_sweep_eval",
 )
+# knn_confusion_device keeps its histograms in LDS per wave up to CONF_SMALL_C
+# classes, per workgroup up to CONF_LDS_C, and counts with global atomics
+# beyond; knn_vote_counts_device keeps LDS counters up to COUNTS_LDS_C classes
+CONF_SMALL_C, CONF_LDS_C, COUNTS_LDS_C = 16, 96, 1024
 GROUP_RCCL = 0x100  # knn_group_create mode flag: RCCL collectives also at one GPU
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1, 2
 PRECISION_AUTO, PRECISION_FP32, PRECISION_BF16X3, PRECISION_FP16 = 0, 1, 2, 3
@@ -146,6 +153,15 @@ def lib():
         "knn_loo_sweep_device": ([P, i64, i64, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
         "knn_loo_sweep": ([P, P, i32, i32, P, P, P, P, P], ctypes.c_int),
         "knn_group_loo_sweep": ([P, P, i32, i32, P, P], ctypes.c_int),
+        "knn_confusion_device": ([P, P, i32, i64, P, i32, P, P, P], ctypes.c_int),
+        "knn_vote_counts_device": ([P, P, i64, i32, P, i64, i32, i32, P, P], ctypes.c_int),
+        "knn_classify_sweep_eval_device": ([P, P, i64, P, P, i32, i32, P, P, P, P, P, P],
+                                           ctypes.c_int),
+        "knn_loo_sweep_eval_device": ([P, i64, i64, P, i32, i32, P, P, P, P, P], ctypes.c_int),
+        "knn_classify_sweep_eval": ([P, P, i64, P, i32, i32, P, P, P, P, P], ctypes.c_int),
+        "knn_loo_sweep_eval": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
+        "knn_group_classify_sweep_eval": ([P, P, i64, P, i32, i32, P, P, P, P, P], ctypes.c_int),
+        "knn_group_loo_sweep_eval": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -193,6 +209,7 @@ class Classifier:
         self.device = device
         self.n_train = 0
         self.dim = 0
+        self.class_cnt = 0
 
     def close(self):
         if self._h:
@@ -214,32 +231,58 @@ class Classifier:
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         n, d = X.shape
         _check(lib().knn_set_train(self._h, _ptr(X), _ptr(labels), n, d, int(class_cnt)))
-        self.n_train, self.dim = n, d
+        self.n_train, self.dim, self.class_cnt = n, d, int(class_cnt)
         self._keep = None
+        self._lab = (labels, None, 0)  # (host labels, device pointer, idx_offset) for the counts
 
     def set_train_device(self, dX_ptr, dlab_ptr, n, d, class_cnt, idx_offset=0, keep=None):
         """Device pointers (e.g. torch tensors' data_ptr()); `keep` holds the
         owning objects alive for the library (the pointers are borrowed)."""
         _check(lib().knn_set_train_device(self._h, dX_ptr, dlab_ptr, n, d, int(class_cnt),
                                           int(idx_offset)))
-        self.n_train, self.dim = n, d
+        self.n_train, self.dim, self.class_cnt = n, d, int(class_cnt)
         self._keep = keep
+        self._lab = (None, dlab_ptr, int(idx_offset))
 
-    def classify(self, Q, k, metric=L2, return_neighbors=False):
-        """Returns labels (int32[m]) and, if requested, (idx[m,k], dist[m,k], flags[m])."""
+    def classify(self, Q, k, metric=L2, return_neighbors=False, return_counts=False):
+        """Returns labels (int32[m]) and, if requested, (idx[m,k], dist[m,k], flags[m]).
+        return_counts appends counts int32[m, class_cnt]: how many of the k
+        reported neighbours carry each label (knn_vote_counts_device over the
+        rows the call reports; staged through torch device tensors)."""
         Q = _f64(Q)
         m = Q.shape[0]
         labels = np.empty(m, np.int32)
         flags = np.empty(m, np.int32)
-        idx = np.empty((m, max(k, 1)), np.int64) if return_neighbors else None
+        rows = return_neighbors or return_counts
+        idx = np.empty((m, max(k, 1)), np.int64) if rows else None
         dist = np.empty((m, max(k, 1)), np.float64) if return_neighbors else None
         _check(lib().knn_classify(self._h, _ptr(Q), m, int(k), int(metric), _ptr(labels),
                                   _ptr(idx), _ptr(dist), _ptr(flags)))
+        out = (labels,)
         if return_neighbors:
-            return labels, idx[:, :k], dist[:, :k], flags
-        return labels
+            out += (idx[:, :k], dist[:, :k], flags)
+        if return_counts:
+            out += (self._counts_of(idx, int(k)),)
+        return out[0] if len(out) == 1 else out
 
-    def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False, exclude=None):
+    def _counts_of(self, idx, k):
+        import torch
+        if self.class_cnt <= 0:
+            raise KnnError("vote counts before set_train")
+        dev = torch.device("cuda", self.device)
+        m, kmax = idx.shape
+        host_lab, dlab_ptr, base = self._lab
+        dI = torch.from_numpy(idx).to(dev)
+        dL = torch.tensor(host_lab).to(dev) if host_lab is not None else None
+        dC = torch.empty((m, self.class_cnt), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the context's stream is not torch's
+        self.vote_counts_device(dI.data_ptr(), m, kmax, dlab_ptr if dL is None else dL.data_ptr(),
+                                k, self.class_cnt, dC.data_ptr(), idx_base=base)
+        self.sync()
+        return dC.cpu().numpy()
+
+    def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False, exclude=None,
+                       confusion=False):
         """Labels for every K of `ks` (any order, duplicates allowed) from one
         search at max(ks): labels int32[nk, m], row i for ks[i].  With `truth`
         (int32[m]) also correct int64[nk] = (labels[i] == truth).sum().  With
@@ -247,7 +290,11 @@ class Classifier:
         `exclude` (int64[m], global train indices, -1 = none): query i is
         answered as if train row exclude[i] were not in the train set
         (knn_classify_sweep_excl_device; staged through torch device tensors);
-        then every K <= n_train - 1."""
+        then every K <= n_train - 1.
+        confusion=True (needs `truth`; not with return_neighbors) appends conf
+        int64[nk, C, C] (row = true class, column = predicted) and unl
+        int64[nk] (queries whose label or truth is outside [0, C)):
+        returns (labels, correct, conf, unl)."""
         Q = _f64(Q)
         m = Q.shape[0]
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
@@ -261,7 +308,23 @@ class Classifier:
             exclude = np.ascontiguousarray(exclude, dtype=np.int64)
             if exclude.shape != (m,):
                 raise ValueError("exclude must have one train index (or -1) per query")
+            if confusion:
+                if truth is None or return_neighbors:
+                    raise ValueError("confusion needs truth and excludes return_neighbors")
+                return self._sweep_eval_excl(Q, exclude, ks, metric, truth)
             return self._sweep_excl(Q, exclude, ks, kmax, metric, truth, return_neighbors)
+        if confusion:
+            if truth is None or return_neighbors:
+                raise ValueError("confusion needs truth and excludes return_neighbors")
+            C = self.class_cnt
+            labels = np.empty((nk, m), np.int32)
+            correct = np.zeros(nk, np.int64)
+            conf = np.zeros((nk, C, C), np.int64)
+            unl = np.zeros(nk, np.int64)
+            _check(lib().knn_classify_sweep_eval(self._h, _ptr(Q), m, _ptr(ks), nk, int(metric),
+                                                 _ptr(labels), _ptr(truth), _ptr(correct),
+                                                 _ptr(conf), _ptr(unl)))
+            return labels, correct, conf, unl
         labels = np.empty((nk, m), np.int32)
         flags = np.empty(m, np.int32)
         idx = np.empty((m, max(kmax, 1)), np.int64) if return_neighbors else None
@@ -299,15 +362,88 @@ class Classifier:
             out += (dI.cpu().numpy()[:, :kmax], dD.cpu().numpy()[:, :kmax], dF.cpu().numpy())
         return out[0] if len(out) == 1 else out
 
-    def loo_sweep(self, ks, metric=L2, return_neighbors=False):
+    def _sweep_eval_excl(self, Q, exclude, ks, metric, truth):
+        import torch
+        dev = torch.device("cuda", self.device)
+        m, nk, C = Q.shape[0], ks.shape[0], self.class_cnt
+        dQ = torch.from_numpy(Q).to(dev)
+        dE = torch.from_numpy(exclude).to(dev)
+        dT = torch.from_numpy(truth).to(dev)
+        dL = torch.empty((nk, m), dtype=torch.int32, device=dev)
+        dC = torch.empty(nk, dtype=torch.int64, device=dev)
+        dF = torch.empty((nk, C, C), dtype=torch.int64, device=dev)
+        dU = torch.empty(nk, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)  # the context's stream is not torch's
+        self.classify_sweep_eval_device(dQ.data_ptr(), m, ks, metric, dT.data_ptr(),
+                                        d_labels=dL.data_ptr(), d_correct=dC.data_ptr(),
+                                        d_conf=dF.data_ptr(), d_unl=dU.data_ptr(),
+                                        d_excl=dE.data_ptr())
+        self.sync()
+        return dL.cpu().numpy(), dC.cpu().numpy(), dF.cpu().numpy(), dU.cpu().numpy()
+
+    def classify_sweep_eval_device(self, dQ_ptr, m, ks, metric, d_truth, d_labels=None,
+                                   d_correct=None, d_conf=None, d_unl=None, d_excl=None,
+                                   stream=None):
+        """Device-pointer sweep with the per-class evaluation (enqueue only):
+        d_truth [m] required; d_labels [nk][m], d_correct [nk], d_conf
+        [nk][C][C] and d_unl [nk] optional, zeroed by the call; d_excl as in
+        classify_sweep_device."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_classify_sweep_eval_device(self._h, dQ_ptr, m, d_excl, _ptr(ks),
+                                                    ks.shape[0], int(metric), d_labels, d_truth,
+                                                    d_correct, d_conf, d_unl, stream))
+
+    def loo_sweep_eval_device(self, row0, rows, ks, metric, d_labels=None, d_correct=None,
+                              d_conf=None, d_unl=None, stream=None):
+        """loo_sweep_device with the per-class evaluation (truth = the rows'
+        own labels); every output optional, zeroed by the call."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_loo_sweep_eval_device(self._h, int(row0), int(rows), _ptr(ks),
+                                               ks.shape[0], int(metric), d_labels, d_correct,
+                                               d_conf, d_unl, stream))
+
+    def confusion_device(self, d_labels, nk, m, d_truth, class_cnt, d_conf, d_unl=None,
+                         stream=None):
+        """conf[i][t][p] += #{q : truth[q] == t, labels[i][q] == p} over device
+        labels [nk][m] and truth [m]; unl[i] += the queries outside [0,
+        class_cnt).  ADDS into d_conf int64[nk][C][C] / d_unl int64[nk]: zero
+        them first.  Needs no train set."""
+        _check(lib().knn_confusion_device(self._h, d_labels, int(nk), int(m), d_truth,
+                                          int(class_cnt), d_conf, d_unl, stream))
+
+    def vote_counts_device(self, d_idx, m, kmax, d_lab, k, class_cnt, d_counts, idx_base=0,
+                           stream=None):
+        """counts int32[m][class_cnt] of the labels d_lab[idx - idx_base] among
+        the first k entries of ordered rows d_idx [m][kmax] (-1 = empty slot)."""
+        _check(lib().knn_vote_counts_device(self._h, d_idx, int(m), int(kmax), d_lab,
+                                            int(idx_base), int(k), int(class_cnt), d_counts,
+                                            stream))
+
+    def loo_sweep(self, ks, metric=L2, return_neighbors=False, confusion=False, labels=True):
         """Leave-one-out K sweep over the whole train set (knn_loo_sweep): every
         train row classified against all the OTHER train rows at every K of
         `ks` (each <= n_train - 1).  Returns (labels int32[nk, n], correct
         int64[nk]) and with return_neighbors also (idx[n, kmax], dist[n, kmax],
-        flags[n]); accuracy at ks[i] = correct[i] / n."""
+        flags[n]); accuracy at ks[i] = correct[i] / n.
+        confusion=True (not with return_neighbors) appends conf int64[nk, C, C]
+        and unl int64[nk]; with labels=False no [nk, n] label array is made
+        anywhere and the result is (correct, conf, unl)."""
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
         nk, n = ks.shape[0], self.n_train
         kmax = int(ks.max()) if nk else 0
+        if confusion:
+            if return_neighbors:
+                raise ValueError("confusion excludes return_neighbors")
+            C = self.class_cnt
+            out_lab = np.empty((nk, n), np.int32) if labels else None
+            correct = np.zeros(nk, np.int64)
+            conf = np.zeros((nk, C, C), np.int64)
+            unl = np.zeros(nk, np.int64)
+            _check(lib().knn_loo_sweep_eval(self._h, _ptr(ks), nk, int(metric), _ptr(out_lab),
+                                            _ptr(correct), _ptr(conf), _ptr(unl)))
+            return (out_lab, correct, conf, unl) if labels else (correct, conf, unl)
+        if not labels:
+            raise ValueError("labels=False needs confusion=True")
         labels = np.empty((nk, n), np.int32)
         correct = np.zeros(nk, np.int64)
         flags = np.empty(n, np.int32)
@@ -493,6 +629,7 @@ class Group:
         arr = (ctypes.c_int * len(devices))(*devices)
         flags = GROUP_RCCL if rccl else 0
         self.n_train = 0
+        self.class_cnt = 0
         _check(lib().knn_group_create(ctypes.byref(self._h), len(devices), arr, int(mode) | flags))
 
     def transport(self):
@@ -524,6 +661,7 @@ class Group:
         n, d = X.shape
         _check(lib().knn_group_set_train(self._h, _ptr(X), _ptr(labels), n, d, int(class_cnt)))
         self.n_train = n
+        self.class_cnt = int(class_cnt)
 
     def classify(self, Q, k, metric=L2, return_neighbors=False):
         Q = _f64(Q)
@@ -538,9 +676,11 @@ class Group:
             return labels, idx[:, :k], dist[:, :k], flags
         return labels
 
-    def classify_sweep(self, Q, ks, metric=L2, truth=None):
+    def classify_sweep(self, Q, ks, metric=L2, truth=None, confusion=False):
         """Classifier.classify_sweep over the group: labels int32[nk, m], and
-        with `truth` also correct int64[nk] (summed over the ranks)."""
+        with `truth` also correct int64[nk] (summed over the ranks); with
+        confusion=True (needs truth) also conf int64[nk, C, C] and unl
+        int64[nk], summed over the ranks."""
         Q = _f64(Q)
         m = Q.shape[0]
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
@@ -551,15 +691,39 @@ class Group:
             if truth.shape != (m,):
                 raise ValueError("truth must have one label per query")
         correct = np.zeros(nk, np.int64) if truth is not None else None
+        if confusion:
+            if truth is None:
+                raise ValueError("confusion needs truth")
+            C = self.class_cnt
+            conf = np.zeros((nk, C, C), np.int64)
+            unl = np.zeros(nk, np.int64)
+            _check(lib().knn_group_classify_sweep_eval(self._h, _ptr(Q), m, _ptr(ks), nk,
+                                                       int(metric), _ptr(labels), _ptr(truth),
+                                                       _ptr(correct), _ptr(conf), _ptr(unl)))
+            return labels, correct, conf, unl
         _check(lib().knn_group_classify_sweep(self._h, _ptr(Q), m, _ptr(ks), nk, int(metric),
                                               _ptr(labels), _ptr(truth), _ptr(correct)))
         return labels if truth is None else (labels, correct)
 
-    def loo_sweep(self, ks, metric=L2):
+    def loo_sweep(self, ks, metric=L2, confusion=False, labels=True):
         """Classifier.loo_sweep over the group (mode 0; mode 1 raises KnnError):
-        labels int32[nk, n] in train row order, correct int64[nk]."""
+        labels int32[nk, n] in train row order, correct int64[nk]; with
+        confusion=True also conf int64[nk, C, C] and unl int64[nk], and with
+        labels=False then (correct, conf, unl) alone."""
         ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
         nk = ks.shape[0]
+        if confusion:
+            C = self.class_cnt
+            out_lab = np.empty((nk, self.n_train), np.int32) if labels else None
+            correct = np.zeros(nk, np.int64)
+            conf = np.zeros((nk, C, C), np.int64)
+            unl = np.zeros(nk, np.int64)
+            _check(lib().knn_group_loo_sweep_eval(self._h, _ptr(ks), nk, int(metric),
+                                                  _ptr(out_lab), _ptr(correct), _ptr(conf),
+                                                  _ptr(unl)))
+            return (out_lab, correct, conf, unl) if labels else (correct, conf, unl)
+        if not labels:
+            raise ValueError("labels=False needs confusion=True")
         labels = np.empty((nk, self.n_train), np.int32)
         correct = np.zeros(nk, np.int64)
         _check(lib().knn_group_loo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(labels),

@@ -231,6 +231,77 @@ int knn_loo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t
 int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
                   int64_t* out_correct, int64_t* out_idx, double* out_dist, int32_t* out_flags);
 
+/* ---- per-class evaluation: the confusion matrix at every K, vote counts.
+ * The reference reports one cnt per run (cpp:341-343).  These calls report,
+ * for every K of a sweep, the C x C confusion matrix
+ *   conf[i][t][p] = #{q : truth[q] == t and labels[i][q] == p}   (int64,
+ *   [nk][C][C], row = true class, column = predicted class),
+ *   unl[i] = #{q : labels[i][q] or truth[q] outside [0, C)}       (int64, [nk])
+ * (label -1 at K = 0 or for a non-finite query; any truth value the caller
+ * supplies -- nothing is read or written out of bounds for any of them), so
+ * sum(conf[i]) + unl[i] == m, and trace(conf[i]) == correct[i] whenever every
+ * truth lies in [0, C).  They are defined by the sweep's labels alone, i.e. by
+ * the reference's neighbour order and its first-to-strictly-exceed vote
+ * (cpp:324-337).
+ * Ties: labels equal the reference's at the default "ties" = 1, so conf equals
+ * the reference's.  Vote COUNTS depend on which rows are among the k nearest
+ * when dist[k-1] == dist[k] (KNN_FLAG_TIE_BOUNDARY): at "ties" = 1 a boundary
+ * tie that cannot change the label is ordered by train index, and the counts
+ * are those of the rows the call reports (idx); they equal the reference's
+ * top-k membership under "ties" = 2.
+ *
+ * knn_confusion_device: the building block over any label array d_labels
+ * [nk][m] (the sweep's layout) and d_truth [m]; needs no train set.  It ADDS
+ * into d_conf [nk*C*C] and d_unl [nk] (nullable): the caller zeroes them, and
+ * two calls into the same buffers give the sum.  1 <= nk <= 4096, class_cnt
+ * >= 1.  The histograms are kept in LDS per wave for class_cnt <= 16, per
+ * workgroup for class_cnt <= 96, and counted with global atomics beyond.
+ * Device pointers; enqueue only. */
+int knn_confusion_device(knn_ctx* ctx, const int32_t* d_labels, int32_t nk, int64_t m,
+                         const int32_t* d_truth, int32_t class_cnt, int64_t* d_conf,
+                         int64_t* d_unl, void* stream);
+/* Vote counts (the reference's label_cnt[] after cpp:324-337, predict_proba
+ * times k): d_counts [m][class_cnt] (int32), counts[q][c] = #{t < k : label of
+ * row entry t == c} over ordered neighbour rows d_idx [m][kmax] with label
+ * d_lab[idx - idx_base], as knn_vote_sweep_device reads them.  0 <= k <= kmax
+ * (KNN_ERR_ARG names both otherwise).  Entries with idx -1 are skipped, a row
+ * without neighbours gives all zeros: a row sums to min(k, its valid
+ * entries).  Every cell of d_counts is written.  Enqueue only. */
+int knn_vote_counts_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_t kmax,
+                           const int32_t* d_lab, int64_t idx_base, int32_t k, int32_t class_cnt,
+                           int32_t* d_counts, void* stream);
+/* knn_classify_sweep_excl_device (d_excl NULL: the plain sweep) plus the
+ * evaluation at class_cnt = the train set's.  d_truth [m] is required
+ * (KNN_ERR_ARG); d_labels [nk*m], d_correct [nk], d_conf [nk*C*C] and d_unl
+ * [nk] are each nullable (without d_labels the labels live in the context's
+ * workspace).  Zero-or-accumulate: like d_correct in the device sweeps, d_conf
+ * and d_unl are ZEROED by the call on its stream and then hold this call's
+ * counts alone; to sum several calls, add the results or use
+ * knn_confusion_device, which accumulates.  Enqueue only; KNN_ERR_STATE before
+ * set_train. */
+int knn_classify_sweep_eval_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                   const int64_t* d_excl, const int32_t* ks, int32_t nk,
+                                   int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                   int64_t* d_correct, int64_t* d_conf, int64_t* d_unl,
+                                   void* stream);
+/* knn_loo_sweep_device plus the evaluation: truth is the rows' own labels.
+ * d_labels [nk*rows], d_correct, d_conf, d_unl nullable; zeroed by the call. */
+int knn_loo_sweep_eval_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks,
+                              int32_t nk, int32_t metric, int32_t* d_labels, int64_t* d_correct,
+                              int64_t* d_conf, int64_t* d_unl, void* stream);
+/* Host twins (wait for the result).  truth [m] required; out_labels [nk*m],
+ * out_correct [nk], out_conf [nk*C*C], out_unl [nk] each nullable. */
+int knn_classify_sweep_eval(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks,
+                            int32_t nk, int32_t metric, int32_t* out_labels, const int32_t* truth,
+                            int64_t* out_correct, int64_t* out_conf, int64_t* out_unl);
+/* Leave-one-out over all n_train rows in the 16384-row batches of
+ * knn_loo_sweep; out_conf / out_unl are summed over the batches on the device.
+ * Without out_labels no [nk][n] array exists anywhere: the label workspace is
+ * [nk][16384]. */
+int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric,
+                       int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                       int64_t* out_unl);
+
 /* Train-sharded building block: exact top-w of THIS context's shard for
  * each query, sorted by (dist, global idx), with each neighbour's label.
  * Rows beyond the shard size are padded with dist=+inf, idx=-1, label=-1.
@@ -494,6 +565,20 @@ int knn_group_classify_sweep(knn_group* g, const double* Q, int64_t m, const int
  * KNN_ERR_ARG with a message saying so. */
 int knn_group_loo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
                         int32_t* out_labels, int64_t* out_correct);
+/* The group sweeps with the per-class evaluation (see knn_classify_sweep_eval
+ * and knn_loo_sweep_eval): truth [m] required for the classify sweep;
+ * out_labels, out_correct, out_conf [nk*C*C] and out_unl [nk] each nullable;
+ * every rank evaluates its own slice on its GPU and the host sums conf / unl
+ * over the ranks, as it sums out_correct.  knn_group_classify_sweep_eval
+ * serves modes 0 and 1; knn_group_loo_sweep_eval serves mode 0 and refuses
+ * mode 1 (train-sharded) with the message of knn_group_loo_sweep. */
+int knn_group_classify_sweep_eval(knn_group* g, const double* Q, int64_t m, const int32_t* ks,
+                                  int32_t nk, int32_t metric, int32_t* out_labels,
+                                  const int32_t* truth, int64_t* out_correct, int64_t* out_conf,
+                                  int64_t* out_unl);
+int knn_group_loo_sweep_eval(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                             int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                             int64_t* out_unl);
 /* Seconds of the last group classify spent between the first enqueue and
  * the last device completion (device-resident inputs, excludes H2D/D2H). */
 double knn_group_last_compute_seconds(knn_group* g);
