@@ -1029,6 +1029,19 @@ static int sweep_upload(knn_ctx* ctx, const int32_t* ks, int32_t nk, int64_t* d_
   return KNN_OK;
 }
 
+// the prefix votes over a call's finished rows in the context's vote mode
+// (knn_sweep.hip / knn_wvote.hip)
+static void sweep_votes(knn_ctx* ctx, const int64_t* idx, const double* dist, int64_t m, int kmax,
+                        const int* dks, int nk, int32_t* d_labels, const int32_t* d_truth,
+                        int64_t* d_correct, hipStream_t s) {
+  if (ctx->vote == KNN_VOTE_DISTANCE)
+    launch_wvote_sweep(idx, dist, m, kmax, ctx->train.lab, ctx->idx_off, dks, nk, d_labels,
+                       d_truth, (unsigned long long*)d_correct, ctx->cu_count, s);
+  else
+    launch_sweep_vote(idx, m, kmax, ctx->train.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
+                      (unsigned long long*)d_correct, ctx->cu_count, s);
+}
+
 static int check_query_args(knn_ctx* ctx, int64_t m, int32_t k, int32_t metric) {
   if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "classify before set_train");
   if (m < 0) return knn_fail(KNN_ERR_ARG, "m must be >= 0");
@@ -1123,6 +1136,25 @@ int knn_classify_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t k, in
   sink.dist = d_dist;
   sink.flags = d_flags;
   const int W = (int)std::min<int64_t>((int64_t)k + 1, ctx->train.n);
+  if (ctx->vote == KNN_VOTE_DISTANCE) {
+    // the search and its tie pass as in uniform mode, into internal rows where
+    // the caller passes none; then the weighted vote over those rows replaces
+    // the labels (a one-entry list of K)
+    if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * k * sizeof(int64_t)))) return rc;
+    if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * k * sizeof(double)))) return rc;
+    if ((rc = ctx->sw_ks.ensure(sizeof(int32_t)))) return rc;
+    if (!d_idx) sink.idx = (int64_t*)ctx->sw_idx.p;
+    if (!d_dist) sink.dist = (double*)ctx->sw_dist.p;
+    rc = k > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
+                   : knn_run_search(ctx, dQ, m, W, metric, sink, s);
+    if (rc) return rc;
+    launch_fill_i32((int32_t*)ctx->sw_ks.p, 1, k, s);
+    launch_wvote_sweep(sink.idx, sink.dist, m, k, ctx->train.lab, ctx->idx_off,
+                       (const int*)ctx->sw_ks.p, 1, d_labels, nullptr, nullptr, ctx->cu_count, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+    return KNN_OK;
+  }
   if (k > kMaxK) return run_large_k(ctx, dQ, m, W, metric, sink, s);
   return knn_run_search(ctx, dQ, m, W, metric, sink, s);
 }
@@ -1240,8 +1272,7 @@ int knn_classify_sweep_device(knn_ctx* ctx, const double* dQ, int64_t m, const i
                           sink.tie_mode, sink.tie_q, sink.tie_cnt, ctx->cu_count, s);
     tie_order(ctx, ts, metric, dQ, sink, s);
   }
-  launch_sweep_vote(sink.idx, m, kmax, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
-                    (unsigned long long*)d_correct, ctx->cu_count, s);
+  sweep_votes(ctx, sink.idx, sink.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
   return KNN_OK;
@@ -1369,8 +1400,7 @@ int knn_classify_sweep_excl_device(knn_ctx* ctx, const double* dQ, int64_t m,
                           out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
     tie_order(ctx, ts, metric, dQ, out, s, d_excl);
   }
-  launch_sweep_vote(out.idx, m, kmax, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
-                    (unsigned long long*)d_correct, ctx->cu_count, s);
+  sweep_votes(ctx, out.idx, out.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
   return KNN_OK;
@@ -1492,6 +1522,56 @@ int knn_vote_counts_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   HIP_TRY(launch_eval_vote_counts(d_idx, m, kmax, d_lab, idx_base, k, class_cnt, d_counts,
                                   ctx->cu_count, s));
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+// ---- distance-weighted voting over caller-supplied rows (knn_wvote.hip)
+
+int knn_vote_sweep_weighted_device(knn_ctx* ctx, const int64_t* d_idx, const double* d_dist,
+                                   int64_t m, int32_t kmax, const int32_t* d_lab,
+                                   int64_t idx_base, const int32_t* ks, int32_t nk,
+                                   int32_t* d_labels, const int32_t* d_truth, int64_t* d_correct,
+                                   void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  int32_t top = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, kmax, &top))) return rc;
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (kmax > 0 && (!d_idx || !d_dist || !d_lab))
+    return knn_fail(KNN_ERR_ARG, "null neighbour rows / distances / labels");
+  launch_wvote_sweep(d_idx, d_dist, m, kmax, d_lab, idx_base, (const int*)ctx->sw_ks.p, nk,
+                     d_labels, d_truth, (unsigned long long*)d_correct, ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+int knn_vote_weights_device(knn_ctx* ctx, const int64_t* d_idx, const double* d_dist, int64_t m,
+                            int32_t kmax, const int32_t* d_lab, int64_t idx_base, int32_t k,
+                            int32_t class_cnt, double* d_wsum, void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  if (k < 0) return knn_fail(KNN_ERR_ARG, "k must be >= 0");
+  if (k > kmax)
+    return knn_fail(KNN_ERR_ARG, "k = " + std::to_string(k) + " exceeds kmax = " +
+                                     std::to_string(kmax) + " (the entries of a row)");
+  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
+  if (!d_wsum) return knn_fail(KNN_ERR_ARG, "null d_wsum");
+  if (m == 0) return KNN_OK;
+  if (k > 0 && (!d_idx || !d_dist || !d_lab))
+    return knn_fail(KNN_ERR_ARG, "null neighbour rows / distances / labels");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  launch_wvote_sums(d_idx, d_dist, m, kmax, d_lab, idx_base, k, class_cnt, d_wsum,
+                    ctx->cu_count, s);
   HIP_TRY(hipGetLastError());
   return KNN_OK;
 }
@@ -1841,6 +1921,17 @@ int knn_set_precision(knn_ctx* ctx, int mode) {
   ctx->precision = mode;
   return KNN_OK;
 }
+
+int knn_set_vote(knn_ctx* ctx, int mode) {
+  if (!ctx) return knn_fail(KNN_ERR_ARG, "null context");
+  if (mode != KNN_VOTE_UNIFORM && mode != KNN_VOTE_DISTANCE)
+    return knn_fail(KNN_ERR_ARG, "unknown vote mode " + std::to_string(mode) +
+                                     " (0 uniform, 1 distance)");
+  ctx->vote = mode;
+  return KNN_OK;
+}
+
+int knn_get_vote(knn_ctx* ctx) { return ctx ? ctx->vote : -1; }
 
 int knn_last_candidate_path(knn_ctx* ctx) { return ctx ? ctx->last_kmetric : -1; }
 

@@ -35,6 +35,7 @@ struct knn_ctx {
   int64_t idx_off = 0;
   int cu_count = 0;
   int precision = 0;     // KNN_PRECISION_*
+  int vote = 0;          // KNN_VOTE_* (knn_set_vote)
   int DPb = 0;           // padded dim of the bf16x3 copy (0 = not built)
   int DPh = 0;           // padded dim of the fp16 copy (0 = not built)
   int xh_swz = 0;        // the fp16 copy's chunks are swizzled (xh_swz)

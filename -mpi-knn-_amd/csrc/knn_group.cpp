@@ -383,6 +383,18 @@ int knn_group_set_tuning(knn_group* g, const char* key, int64_t value) {
   return KNN_OK;
 }
 
+int knn_group_set_vote(knn_group* g, int mode) {
+  if (!g) return knn_fail(KNN_ERR_ARG, "null group");
+  if (mode != KNN_VOTE_UNIFORM && mode != KNN_VOTE_DISTANCE)  // (before any rank changes)
+    return knn_fail(KNN_ERR_ARG, "unknown vote mode " + std::to_string(mode) +
+                                     " (0 uniform, 1 distance)");
+  for (auto* c : g->ctx) {
+    int rc = knn_set_vote(c, mode);
+    if (rc) return rc;
+  }
+  return KNN_OK;
+}
+
 int knn_group_destroy(knn_group* g) {
   if (!g) return KNN_OK;
   for (int i = 0; i < g->ndev; i++) {
@@ -766,6 +778,21 @@ int knn_group_classify(knn_group* g, const double* Q, int64_t m, int32_t k, int3
   const int ties = g->ctx[0]->tune.ties;
   if ((rc = sharded_search(g, Q, m, k, metric, ties))) return rc;
   if (ties && (rc = resolve_ties(g, m, k, metric))) return rc;
+  if (g->ctx[0]->vote == KNN_VOTE_DISTANCE) {
+    // the weighted vote over each rank's merged rows (a one-entry list of K)
+    // replaces the merge's labels; k lives until finish() has waited
+    for (int i = 0; i < G; i++) {
+      int64_t q0, mi;
+      slice(i, q0, mi);
+      if (mi <= 0) continue;
+      HIP_G(hipSetDevice(g->devs[i]));
+      if ((rc = knn_vote_sweep_weighted_device(
+               g->ctx[i], (const int64_t*)g->oidx[i].p, (const double*)g->odist[i].p, mi, k,
+               (const int32_t*)g->labA[i].p, 0, &k, 1, (int32_t*)g->olab[i].p, nullptr, nullptr,
+               g->ctx[i]->stream)))
+        return rc;
+    }
+  }
   for (int i = 0; i < G; i++) {
     HIP_G(hipSetDevice(g->devs[i]));
     HIP_G(hipEventRecord(g->ev1[i], g->ctx[i]->stream));
@@ -939,12 +966,19 @@ static int group_sweep(knn_group* g, const double* Q, int64_t m, const int32_t* 
       if (truth)
         HIP_G(hipMemcpyAsync(g->struth[i].p, truth + q0, (size_t)mi * sizeof(int32_t),
                              hipMemcpyHostToDevice, s));
-      if ((rc = knn_vote_sweep_device(g->ctx[i], (const int64_t*)g->oidx[i].p, mi, kmax,
-                                      (const int32_t*)g->labA[i].p, 0, ks, nk,
-                                      (int32_t*)g->slab[i].p,
-                                      out_correct ? (const int32_t*)g->struth[i].p : nullptr,
-                                      out_correct ? (int64_t*)g->scorr[i].p : nullptr, s)))
-        return rc;
+      if (g->ctx[i]->vote == KNN_VOTE_DISTANCE)
+        rc = knn_vote_sweep_weighted_device(
+            g->ctx[i], (const int64_t*)g->oidx[i].p, (const double*)g->odist[i].p, mi, kmax,
+            (const int32_t*)g->labA[i].p, 0, ks, nk, (int32_t*)g->slab[i].p,
+            out_correct ? (const int32_t*)g->struth[i].p : nullptr,
+            out_correct ? (int64_t*)g->scorr[i].p : nullptr, s);
+      else
+        rc = knn_vote_sweep_device(g->ctx[i], (const int64_t*)g->oidx[i].p, mi, kmax,
+                                   (const int32_t*)g->labA[i].p, 0, ks, nk,
+                                   (int32_t*)g->slab[i].p,
+                                   out_correct ? (const int32_t*)g->struth[i].p : nullptr,
+                                   out_correct ? (int64_t*)g->scorr[i].p : nullptr, s);
+      if (rc) return rc;
       if (eval) {  // the rank's slice of the labels against its slice of the truth
         HIP_G(hipMemsetAsync(g->sconf[i].p, 0, (size_t)nk * cc * sizeof(int64_t), s));
         HIP_G(hipMemsetAsync(g->sunl[i].p, 0, (size_t)nk * sizeof(int64_t), s));

@@ -439,6 +439,23 @@ constexpr int kEvalCountsLdsC = 1024;
 hipError_t launch_eval_vote_counts(const int64_t* idx, int64_t m, int kmax, const int32_t* lab,
                                    int64_t idx_base, int k, int class_cnt, int32_t* counts,
                                    int cus, hipStream_t s);
+// Distance-weighted voting (knn_wvote.hip; the rule: knn_amd.h,
+// KNN_VOTE_DISTANCE).  Rows idx / dist [m][kmax] ascending by distance, label
+// of an entry lab[idx - idx_base] (idx -1, an index below idx_base or a
+// negative label: the entry does not vote).
+// sweep: launch_sweep_vote's arguments plus dist; labels[j][q] = the weighted
+// label over the first ks[j] entries, correct as there.  Dynamic LDS:
+// wvote_sweep_lds_bytes (<= 64 KB for every kmax and nk <= 4096).
+size_t wvote_sweep_lds_bytes(int kmax, int nk, bool with_truth);
+void launch_wvote_sweep(const int64_t* idx, const double* dist, int64_t m, int kmax,
+                        const int32_t* lab, int64_t idx_base, const int* ks, int nk,
+                        int32_t* labels, const int32_t* truth, unsigned long long* correct, int cus,
+                        hipStream_t s);
+// sums: wsum[q][c] (m x C, fp64) = the class sums after the first k entries (k
+// <= kmax), each class added up in row order; every cell is written
+void launch_wvote_sums(const int64_t* idx, const double* dist, int64_t m, int kmax,
+                       const int32_t* lab, int64_t idx_base, int k, int class_cnt, double* wsum,
+                       int cus, hipStream_t s);
 // fp64 rows -> [hi(DP) | lo(DP)] bf16 rows of scale*x (candidate metric 2 = L2 via bf16x3)
 // rows of `out` are row_shorts 16-bit words; xl2/xl1 (train only, else null)
 // fill the padded row's seed floats after the 2*DP bf16 payload

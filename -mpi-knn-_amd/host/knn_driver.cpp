@@ -33,6 +33,11 @@
 // predicted class) and "unlabelled = <n>" (queries whose label or truth is
 // outside [0, class_cnt)), from knn_group_classify_sweep_eval /
 // knn_group_loo_sweep_eval; without the flag stdout is unchanged.
+// --weights uniform|distance (default uniform): how the neighbours vote
+// (knn_group_set_vote).  distance = each neighbour weighs 1 / its distance and
+// exact matches alone decide (KNN_VOTE_DISTANCE, knn_amd.h); it applies to the
+// validation pass, the test pass, --K_list, --loo and --confusion, and every
+// output keeps its format.
 // The timed region spans the same work as the reference (barrier to
 // barrier: CSV parsing, distribution, normalisation, both passes, output).
 #include <chrono>
@@ -70,6 +75,7 @@ struct Config {
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
   bool confusion = false;       // --confusion: print the selected K's confusion matrix
+  int vote = KNN_VOTE_UNIFORM;  // --weights uniform|distance
   std::vector<std::pair<std::string, long long>> tune;  // --tune KEY=VALUE (knn_set_tuning keys)
 };
 
@@ -82,13 +88,15 @@ void usage() {
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
           "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--confusion]\n"
-          "  [--tune KEY=VALUE]...\n"
+          "  [--tune KEY=VALUE]... [--weights uniform|distance]\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
           "  (no validation file is read)\n"
           "  --confusion prints the confusion matrix of the validation (or --loo) pass at the\n"
           "  selected K: class_cnt rows (true class) of class_cnt counts (predicted class)\n"
+          "  --weights distance: every pass votes with weight 1 / distance (exact matches\n"
+          "  alone decide where there are any); uniform (default) is the reference's vote\n"
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
           "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
           "  (i8l1=2: also at 256 < dim <= 1024); --tune u16l1=1: the L1 pass on 16-bit\n"
@@ -150,6 +158,14 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "K_list") {
       if (!parse_k_list(v, c.K_list)) {
         fprintf(stderr, "--K_list takes a comma-separated list of non-negative integers\n");
+        return 1;
+      }
+    }
+    else if (a == "weights") {
+      if (v == "uniform") c.vote = KNN_VOTE_UNIFORM;
+      else if (v == "distance") c.vote = KNN_VOTE_DISTANCE;
+      else {
+        fprintf(stderr, "--weights takes uniform or distance\n");
         return 1;
       }
     }
@@ -228,6 +244,7 @@ int main(int argc, char** argv) {
   if (knn_group_create(&g, c.gpus, nullptr, c.mode)) die(knn_last_error());
   for (const auto& kv : c.tune)
     if (knn_group_set_tuning(g, kv.first.c_str(), kv.second)) die(knn_last_error());
+  if (knn_group_set_vote(g, c.vote)) die(knn_last_error());
 
   using clk = std::chrono::steady_clock;
   const auto start = clk::now();  // ≙ MPI_Barrier + MPI_Wtime, cpp:133-134

@@ -45,6 +45,8 @@ EXPORTED = (
     "knn_confusion_device", "knn_vote_counts_device", "knn_classify_sweep_eval_device",
     "knn_loo_sweep_eval_device", "knn_classify_sweep_eval", "knn_loo_sweep_eval",
     "knn_group_classify_sweep_eval", "knn_group_loo_sweep_eval",
+    "knn_set_vote", "knn_get_vote", "knn_group_set_vote", "knn_vote_sweep_weighted_device",
+    "knn_vote_weights_device",
 )
 # knn_confusion_device keeps its histograms in LDS per wave up to CONF_SMALL_C
 # classes, per workgroup up to CONF_LDS_C, and counts with global atomics
@@ -54,6 +56,9 @@ GROUP_RCCL = 0x100  # knn_group_create mode flag: RCCL collectives also at one G
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOOPBACK = 0, 1, 2
 PRECISION_AUTO, PRECISION_FP32, PRECISION_BF16X3, PRECISION_FP16 = 0, 1, 2, 3
 PHASE_PREP, PHASE_CANDIDATE, PHASE_RERANK, PHASE_RESCAN = 0, 1, 2, 3
+# vote mode of a context (knn_set_vote): the reference's unweighted vote, or
+# weight 1 / distance with exact matches deciding alone (knn_amd.h)
+VOTE_UNIFORM, VOTE_DISTANCE = 0, 1
 
 
 class KnnError(RuntimeError):
@@ -162,6 +167,12 @@ def lib():
         "knn_loo_sweep_eval": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
         "knn_group_classify_sweep_eval": ([P, P, i64, P, i32, i32, P, P, P, P, P], ctypes.c_int),
         "knn_group_loo_sweep_eval": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
+        "knn_set_vote": ([P, ctypes.c_int], ctypes.c_int),
+        "knn_get_vote": ([P], ctypes.c_int),
+        "knn_group_set_vote": ([P, ctypes.c_int], ctypes.c_int),
+        "knn_vote_sweep_weighted_device": ([P, P, P, i64, i32, P, i64, P, i32, P, P, P, P],
+                                           ctypes.c_int),
+        "knn_vote_weights_device": ([P, P, P, i64, i32, P, i64, i32, i32, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -244,18 +255,23 @@ class Classifier:
         self._keep = keep
         self._lab = (None, dlab_ptr, int(idx_offset))
 
-    def classify(self, Q, k, metric=L2, return_neighbors=False, return_counts=False):
+    def classify(self, Q, k, metric=L2, return_neighbors=False, return_counts=False,
+                 return_weights=False):
         """Returns labels (int32[m]) and, if requested, (idx[m,k], dist[m,k], flags[m]).
         return_counts appends counts int32[m, class_cnt]: how many of the k
         reported neighbours carry each label (knn_vote_counts_device over the
-        rows the call reports; staged through torch device tensors)."""
+        rows the call reports; staged through torch device tensors).
+        return_weights appends wsum float64[m, class_cnt]: the class sums of
+        the distance-weighted vote over the same rows (knn_vote_weights_device;
+        in any vote mode)."""
         Q = _f64(Q)
         m = Q.shape[0]
         labels = np.empty(m, np.int32)
         flags = np.empty(m, np.int32)
-        rows = return_neighbors or return_counts
+        rows = return_neighbors or return_counts or return_weights
         idx = np.empty((m, max(k, 1)), np.int64) if rows else None
-        dist = np.empty((m, max(k, 1)), np.float64) if return_neighbors else None
+        dist = (np.empty((m, max(k, 1)), np.float64) if return_neighbors or return_weights
+                else None)
         _check(lib().knn_classify(self._h, _ptr(Q), m, int(k), int(metric), _ptr(labels),
                                   _ptr(idx), _ptr(dist), _ptr(flags)))
         out = (labels,)
@@ -263,7 +279,27 @@ class Classifier:
             out += (idx[:, :k], dist[:, :k], flags)
         if return_counts:
             out += (self._counts_of(idx, int(k)),)
+        if return_weights:
+            out += (self._weights_of(idx, dist, int(k)),)
         return out[0] if len(out) == 1 else out
+
+    def _weights_of(self, idx, dist, k):
+        import torch
+        if self.class_cnt <= 0:
+            raise KnnError("vote weights before set_train")
+        dev = torch.device("cuda", self.device)
+        m, kmax = idx.shape
+        host_lab, dlab_ptr, base = self._lab
+        dI = torch.from_numpy(idx).to(dev)
+        dD = torch.from_numpy(dist).to(dev)
+        dL = torch.tensor(host_lab).to(dev) if host_lab is not None else None
+        dW = torch.empty((m, self.class_cnt), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)  # the context's stream is not torch's
+        self.vote_weights_device(dI.data_ptr(), dD.data_ptr(), m, kmax,
+                                 dlab_ptr if dL is None else dL.data_ptr(), k, self.class_cnt,
+                                 dW.data_ptr(), idx_base=base)
+        self.sync()
+        return dW.cpu().numpy()
 
     def _counts_of(self, idx, k):
         import torch
@@ -418,6 +454,37 @@ class Classifier:
         _check(lib().knn_vote_counts_device(self._h, d_idx, int(m), int(kmax), d_lab,
                                             int(idx_base), int(k), int(class_cnt), d_counts,
                                             stream))
+
+    def vote_sweep_weighted_device(self, d_idx, d_dist, m, kmax, d_lab, ks, d_labels, idx_base=0,
+                                   d_truth=None, d_correct=None, stream=None):
+        """vote_sweep_device by distance (in any vote mode): d_dist [m][kmax]
+        are the rows' ascending distances; weight 1 / distance, exact matches
+        alone decide (knn_vote_sweep_weighted_device)."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_vote_sweep_weighted_device(self._h, d_idx, d_dist, m, int(kmax), d_lab,
+                                                    int(idx_base), _ptr(ks), ks.shape[0],
+                                                    d_labels, d_truth, d_correct, stream))
+
+    def vote_weights_device(self, d_idx, d_dist, m, kmax, d_lab, k, class_cnt, d_wsum, idx_base=0,
+                            stream=None):
+        """wsum float64[m][class_cnt]: the class sums of the distance-weighted
+        vote after the first k entries of ordered rows d_idx / d_dist [m][kmax],
+        each class summed in row order (knn_vote_weights_device)."""
+        _check(lib().knn_vote_weights_device(self._h, d_idx, d_dist, int(m), int(kmax), d_lab,
+                                             int(idx_base), int(k), int(class_cnt), d_wsum,
+                                             stream))
+
+    def set_vote(self, mode):
+        """VOTE_UNIFORM (default: the reference's vote) or VOTE_DISTANCE:
+        classify, classify_sweep (exclude / confusion included) and loo_sweep
+        then vote with weight 1 / distance over the rows they report, exact
+        matches deciding alone (knn_amd.h).  The search and the reported
+        neighbours do not change.  Another value raises KnnError and keeps the
+        mode."""
+        _check(lib().knn_set_vote(self._h, int(mode)))
+
+    def get_vote(self):
+        return int(lib().knn_get_vote(self._h))
 
     def loo_sweep(self, ks, metric=L2, return_neighbors=False, confusion=False, labels=True):
         """Leave-one-out K sweep over the whole train set (knn_loo_sweep): every
@@ -641,6 +708,10 @@ class Group:
     def set_tuning(self, key, value):
         _check(lib().knn_group_set_tuning(self._h, key.encode(), int(value)))
 
+    def set_vote(self, mode):
+        """Classifier.set_vote on every rank (knn_group_set_vote)."""
+        _check(lib().knn_group_set_vote(self._h, int(mode)))
+
     def last_tie_count(self):
         return int(lib().knn_group_last_tie_count(self._h))
 
@@ -748,7 +819,9 @@ def run_driver(cfg: KnnConfig, workdir, gpus=1, mode="query", extra=()):
     "K = <k> accuracy = <acc>" per K and "selected K = <k>", and the test
     pass runs at the selected K), or ["--loo", "--K_list", "1,3,5"] (no
     validation file: every K is scored by leave-one-out on the train set,
-    "K = <k> loo accuracy = <acc>" per K)."""
+    "K = <k> loo accuracy = <acc>" per K), or ["--weights", "distance"]
+    (every pass votes with weight 1 / distance, Classifier.set_vote; the
+    outputs keep their format)."""
     if not os.path.exists(DRIVER_PATH):
         raise KnnError("driver not built: " + DRIVER_PATH)
     args = [DRIVER_PATH]

@@ -302,6 +302,69 @@ int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metr
                        int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
                        int64_t* out_unl);
 
+/* ---- distance-weighted voting: the second hyperparameter of a KNN classifier.
+ * The vote mode is state of the context, like the precision:
+ *   KNN_VOTE_UNIFORM (default): the reference's first-to-strictly-exceed vote
+ *     (cpp:324-337), every behaviour described above;
+ *   KNN_VOTE_DISTANCE: each neighbour votes with weight 1 / distance.
+ * The rule, for one query with the ordered neighbour row the call itself
+ * reports -- idx[t], dist[t] (the fp64 reference distances), l_t = the label of
+ * idx[t], t = 0 .. kmax-1; empty slots (idx -1) count nothing.  The label at
+ * prefix length K:
+ *   z = #{t < K : dist[t] == 0}     (the row is ascending: the first z entries)
+ *   if z >= 1:  entries t < z have weight 1.0; entries t >= z do not vote
+ *   else:       w_t = 1.0 / dist[t] (IEEE fp64 division, correctly rounded;
+ *                                    1 / inf = 0)
+ *   S[c] = 0 for every class; best = -inf; label = -1
+ *   for t in 0 .. K-1 in row order (voting entries only):
+ *       S[l_t] = S[l_t] + w_t       (one fp64 add per entry, in this order)
+ *       if S[l_t] > best: best = S[l_t]; label = l_t
+ * So exact matches alone decide when there are any (the usual convention);
+ * with unit weights the scan IS the reference's vote, and a row with z >= 1
+ * gets the uniform label at min(K, z); `best` is always the largest class sum
+ * and the label the class that reached it first; K = 0 gives -1, a non-finite
+ * query -1 at every K (KNN_FLAG_NONFINITE), a row whose weights are all 0 the
+ * label l_0 (the first voting entry always records).  The result is
+ * reproducible bit for bit by that sequential loop.  Permuting entries of equal
+ * distance inside the prefix changes no class sum (each class's sequence of
+ * addends stays the same); the order among equal distances matters only at the
+ * membership boundary (dist[K-1] == dist[K]) and when two classes end on
+ * exactly equal sums, and there the label is defined on the rows the call
+ * reports: the reference's std::sort order with "ties" = 2; with "ties" = 1 the
+ * reference's order where the UNIFORM label could depend on it and train-index
+ * order elsewhere.  The search, the tie queue, the flags, idx and dist are
+ * exactly what KNN_VOTE_UNIFORM produces for the same call.
+ * In KNN_VOTE_DISTANCE mode these calls return the rule's labels (correct,
+ * conf and unl follow from them): knn_classify*, knn_classify_sweep* (the
+ * _excl variant included), knn_loo_sweep*, the four *_eval* calls, and the
+ * knn_group_* twins (knn_group_set_vote).  These stay UNIFORM in every mode:
+ * knn_vote_sweep_device, knn_vote_counts_device, knn_merge_vote_device and
+ * knn_tie_resolve_device (building blocks; the weighted ones are below).
+ * knn_set_vote: KNN_ERR_ARG for any other value, the mode is kept. */
+#define KNN_VOTE_UNIFORM 0
+#define KNN_VOTE_DISTANCE 1
+int knn_set_vote(knn_ctx* ctx, int mode);
+/* The context's vote mode (-1 for a null context). */
+int knn_get_vote(knn_ctx* ctx);
+/* knn_vote_sweep_device by distance: its arguments plus d_dist [m][kmax], the
+ * rows' distances (ascending; +inf in empty slots).  Always votes by distance,
+ * whatever the context's mode.  An entry with idx -1 (or a negative label)
+ * does not vote; a row without voting entries gets -1 at every K.  Same
+ * argument checks; device pointers except ks; enqueue only. */
+int knn_vote_sweep_weighted_device(knn_ctx* ctx, const int64_t* d_idx, const double* d_dist,
+                                   int64_t m, int32_t kmax, const int32_t* d_lab,
+                                   int64_t idx_base, const int32_t* ks, int32_t nk,
+                                   int32_t* d_labels, const int32_t* d_truth, int64_t* d_correct,
+                                   void* stream);
+/* The weighted twin of knn_vote_counts_device: d_wsum [m][class_cnt] (fp64) =
+ * the class sums S of the rule after the first k entries (the z rule applied;
+ * predict_proba times the row's total weight), each class summed sequentially
+ * in row order.  0 <= k <= kmax; labels outside [0, class_cnt) count nothing;
+ * every cell is written, zeros for a row without neighbours.  Enqueue only. */
+int knn_vote_weights_device(knn_ctx* ctx, const int64_t* d_idx, const double* d_dist, int64_t m,
+                            int32_t kmax, const int32_t* d_lab, int64_t idx_base, int32_t k,
+                            int32_t class_cnt, double* d_wsum, void* stream);
+
 /* Train-sharded building block: exact top-w of THIS context's shard for
  * each query, sorted by (dist, global idx), with each neighbour's label.
  * Rows beyond the shard size are padded with dist=+inf, idx=-1, label=-1.
@@ -541,6 +604,12 @@ int knn_group_transport(knn_group* g);
 /* knn_set_precision / knn_set_tuning on every rank's context. */
 int knn_group_set_precision(knn_group* g, int mode);
 int knn_group_set_tuning(knn_group* g, const char* key, int64_t value);
+/* knn_set_vote on every rank's context.  KNN_VOTE_DISTANCE: in mode 0 each
+ * rank's context votes by distance; in mode 1 the weighted vote runs over the
+ * merged rows (after the cross-shard tie exchange) with the all-rows label
+ * array, so every mode gives the one-context labels.  knn_group_loo_sweep*
+ * still refuse mode 1. */
+int knn_group_set_vote(knn_group* g, int mode);
 int knn_group_destroy(knn_group* g);
 int knn_group_set_train(knn_group* g, const double* X, const int32_t* labels, int64_t n,
                         int32_t d, int32_t class_cnt);
