@@ -207,16 +207,36 @@ def test_partial_merge_reference_tie_order(knn, metric, ties):
         c.close()
 
 
-@pytest.mark.parametrize("metric", [0, 1])
-def test_hip_ties_default_stream(knn, metric):
+class _CurrentStream:
+    """hip_ties_case's hooks for torch's current stream: nothing to stage."""
+
+    def begin(self, dev, lists, outs):
+        return lists
+
+    def merged(self):
+        pass
+
+    def end(self, ties):
+        import torch
+        torch.cuda.synchronize()
+
+    def close(self):
+        pass
+
+
+def hip_ties_case(knn, metric, hooks=None):
     """knn_dist.resolve_ties through knn_dist.HipTies as bench.py's mode b
-    drives it, here at world 1 and with HipTies' default stream (torch's
-    current one: the flags, the distance blocks and the library calls on one
-    stream): 3 shard contexts' lists merged in one context, every flagged
-    query resolved, labels = the oracle's, none left pending."""
+    drives it, at world 1 and with HipTies' default stream (torch's current
+    one: the flags, the distance blocks and the library calls on one stream):
+    3 shard contexts' lists merged in one context, every flagged query
+    resolved, labels = the oracle's, none left pending.
+    hooks (test_gpu_streams.py): begin(dev, lists, outs) may stage the merge's
+    lists and make another stream current, merged() follows the merge's
+    enqueue, end(ties) waits for the work, close() restores the stream."""
     import importlib.util
     import os
     import torch
+    hooks = hooks or _CurrentStream()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location(
         "knn_dist", os.path.join(root, "-mpi-knn-_amd", "knn_dist.py"))
@@ -240,14 +260,20 @@ def test_hip_ties_default_stream(knn, metric):
             torch.empty((m, k), dtype=torch.int64, device=dev),
             torch.empty((m, k), dtype=torch.float64, device=dev),
             torch.empty(m, dtype=torch.int32, device=dev))
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    c.merge_vote_device(gd.data_ptr(), gi.data_ptr(), gl.data_ptr(), 3, m, w, k,
-                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                        outs[3].data_ptr(), stream=stream)
-    ties = kd.HipTies(c, Q, La, n, k, outs, m, metric=metric, device=dev)
-    resolved = kd.resolve_ties(ties, m, dev)
+    gd, gi, gl = hooks.begin(dev, (gd, gi, gl), outs)
+    try:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.merge_vote_device(gd.data_ptr(), gi.data_ptr(), gl.data_ptr(), 3, m, w, k,
+                            outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                            outs[3].data_ptr(), stream=stream)
+        hooks.merged()
+        ties = kd.HipTies(c, Q, La, n, k, outs, m, metric=metric, device=dev)
+        resolved = kd.resolve_ties(ties, m, dev)
+        hooks.end(ties)
+        got, idx, dist, flags = (t.cpu().numpy() for t in outs)
+    finally:
+        hooks.close()
     torch.cuda.synchronize()
-    got, idx, dist, flags = (t.cpu().numpy() for t in outs)
     want, widx, wdist = oracle.knn(tr, lab, te, k, metric == 0, 5, n_out=k)
     assert resolved > 20 and ties.resolved == resolved
     assert not (flags & knn.FLAG_TIE_PENDING).any()
@@ -255,7 +281,14 @@ def test_hip_ties_default_stream(knn, metric):
     ref = (flags & knn.FLAG_TIE_REF) != 0
     np.testing.assert_array_equal(idx[ref], widx[ref])
     assert_neighbors_match(idx, dist, widx, wdist, flags)
+    c.sync()
     c.close()
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+def test_hip_ties_default_stream(knn, metric):
+    """hip_ties_case on torch's current (legacy default) stream."""
+    hip_ties_case(knn, metric)
 
 
 @pytest.mark.parametrize("k", [7, 1500])
