@@ -7,15 +7,24 @@
 // knn_cand.hip / knn_select.hip; there is no host compute path.
 #include <hip/hip_runtime.h>
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <algorithm>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <thread>
+#include <vector>
 
 #include "../../include/knn_amd.h"
 #include "knn_api_internal.h"
+#include "knn_csv_num.h"
 #include "knn_kernels.h"
 
 using namespace knnk;
@@ -1865,6 +1874,304 @@ int knn_normalize(knn_ctx* ctx, double* const* sets, const int64_t* rows, int32_
   if (out_max) HIP_TRY(hipMemcpyAsync(out_max, dmax, d * sizeof(double), hipMemcpyDeviceToHost, s));
   if (out_min) HIP_TRY(hipMemcpyAsync(out_min, dmin, d * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return KNN_OK;
+}
+
+}  // extern "C"
+
+// ---- CSV reader (knn_csv.hip, knn_csv_num.h; replaces cpp:154-222)
+
+namespace {
+
+using csv_clock = std::chrono::steady_clock;
+double csv_secs(csv_clock::time_point a, csv_clock::time_point b) {
+  return std::chrono::duration<double>(b - a).count();
+}
+
+// the conversion table, generated once per process and uploaded once per
+// context (a blocking copy: complete for every stream when it returns)
+int csv_ensure_table(knn_ctx* ctx) {
+  if (ctx->csv_tab_ready) return KNN_OK;
+  static const knncsv::NumTable* host = [] {
+    auto* t = new knncsv::NumTable;
+    knncsv::csv_build_num_table(t);
+    return t;
+  }();
+  int rc;
+  if ((rc = ctx->csv_tab.ensure(sizeof(knncsv::NumTable)))) return rc;
+  HIP_TRY(hipMemcpy(ctx->csv_tab.p, host, sizeof(knncsv::NumTable), hipMemcpyHostToDevice));
+  ctx->csv_tab_ready = true;
+  return KNN_OK;
+}
+
+int csv_token_cap(int dim, bool with_label, int64_t rows, int64_t* cap) {
+  const int64_t per = (int64_t)dim + (with_label ? 1 : 0);
+  if (rows > INT64_MAX / per) return knn_fail(KNN_ERR_ARG, "rows * (dim [+ 1]) overflows");
+  *cap = rows * per;
+  return KNN_OK;
+}
+
+// count + scan + convert (convert alone when convert_only: the block bases of
+// the previous call on the same text are still in the workspace); enqueue only
+int csv_enqueue(knn_ctx* ctx, const char* d_text, int64_t bytes, int dim, bool with_label,
+                int64_t cap, double* d_data, int32_t* d_labels, int64_t* d_tokens,
+                int64_t* d_slow, int64_t slow_cap, int64_t* d_nslow, bool convert_only,
+                hipStream_t s) {
+  int rc;
+  HIP_TRY(hipMemsetAsync(d_nslow, 0, sizeof(int64_t), s));
+  if (bytes == 0) {
+    HIP_TRY(hipMemsetAsync(d_tokens, 0, sizeof(int64_t), s));
+    return KNN_OK;
+  }
+  if ((rc = csv_ensure_table(ctx))) return rc;
+  const int64_t nblk = csv_block_count(bytes);
+  if (nblk > (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "CSV text too large");
+  const size_t base_off = ((size_t)nblk * sizeof(unsigned int) + 15) & ~(size_t)15;
+  if ((rc = ctx->csv_ws.ensure(base_off + (size_t)nblk * sizeof(int64_t)))) return rc;
+  unsigned int* cnt = (unsigned int*)ctx->csv_ws.p;
+  int64_t* base = (int64_t*)((char*)ctx->csv_ws.p + base_off);
+  if (!convert_only) launch_csv_count_scan(d_text, bytes, cnt, base, d_tokens, s);
+  launch_csv_convert(d_text, bytes, base, (const knncsv::NumTable*)ctx->csv_tab.p, dim, with_label,
+                     cap, d_data, d_labels, d_slow, slow_cap, d_nslow, s);
+  HIP_TRY(hipGetLastError());
+  return KNN_OK;
+}
+
+// the whole file into buf (parallel pread of equal byte ranges, at most 16
+// threads), 16 spare bytes behind it
+int csv_slurp(const char* path, std::unique_ptr<char[]>& buf, int64_t* bytes) {
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return knn_fail(KNN_ERR_ARG, std::string("cannot open ") + path);
+  struct stat st;
+  if (fstat(fd, &st) != 0 || st.st_size < 0 || !S_ISREG(st.st_mode)) {
+    close(fd);
+    return knn_fail(KNN_ERR_ARG, std::string("cannot size ") + path);
+  }
+  const size_t sz = (size_t)st.st_size;
+  buf.reset(new char[sz + 16]);
+  int threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  if (sz < (1u << 20)) threads = 1;
+  std::vector<int> bad(threads, 0);
+  const auto part = [&](int t) {
+    size_t o = sz * t / threads;
+    const size_t end = sz * (t + 1) / threads;
+    while (o < end) {
+      const ssize_t got = pread(fd, buf.get() + o, end - o, (off_t)o);
+      if (got <= 0) {
+        bad[t] = 1;
+        return;
+      }
+      o += (size_t)got;
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (int t = 1; t < threads; t++) th.emplace_back(part, t);
+    part(0);
+    for (auto& x : th) x.join();
+  }
+  close(fd);
+  for (int t = 0; t < threads; t++)
+    if (bad[t]) return knn_fail(KNN_ERR_ARG, std::string("short read on ") + path);
+  *bytes = (int64_t)sz;
+  return KNN_OK;
+}
+
+// File -> device values: reads and uploads the text, parses it into d_data /
+// d_labels and fetches the slow list (every slow token: the convert step runs
+// once more when the first capacity was too small).  Waits for the device.
+int csv_read_core(knn_ctx* ctx, const char* path, int dim, bool with_label, int64_t rows,
+                  int64_t cap, double* d_data, int32_t* d_labels, std::unique_ptr<char[]>& buf,
+                  int64_t* bytes, std::vector<int64_t>& slow, int64_t* tokens) {
+  int rc;
+  hipStream_t s = ctx->stream;
+  for (double& v : ctx->csv_phase_s) v = 0.0;
+  ctx->csv_last_slow = -1;
+  const auto t0 = csv_clock::now();
+  if ((rc = csv_slurp(path, buf, bytes))) return rc;
+  const auto t1 = csv_clock::now();
+  if ((rc = ctx->csv_text.ensure((size_t)*bytes + 16))) return rc;
+  if (*bytes > 0)
+    HIP_TRY(hipMemcpyAsync(ctx->csv_text.p, buf.get(), (size_t)*bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const auto t2 = csv_clock::now();
+  int64_t slow_cap = std::max<int64_t>(4096, *bytes / 64);
+  if ((rc = ctx->csv_slow.ensure((size_t)slow_cap * 2 * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->csv_misc.ensure(2 * sizeof(int64_t)))) return rc;
+  int64_t* misc = (int64_t*)ctx->csv_misc.p;  // {tokens, slow count}
+  int64_t h[2] = {0, 0};
+  for (int pass = 0; pass < 2; ++pass) {
+    if ((rc = csv_enqueue(ctx, (const char*)ctx->csv_text.p, *bytes, dim, with_label, cap, d_data,
+                          d_labels, misc, (int64_t*)ctx->csv_slow.p, slow_cap, misc + 1, pass == 1,
+                          s)))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(h, misc, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h[1] <= slow_cap) break;
+    if (pass == 1) return knn_fail(KNN_ERR_DEVICE, "CSV slow list overflowed twice");
+    slow_cap = h[1];  // every slow token this time
+    if ((rc = ctx->csv_slow.ensure((size_t)slow_cap * 2 * sizeof(int64_t)))) return rc;
+  }
+  slow.resize((size_t)h[1] * 2);
+  if (h[1] > 0) {
+    HIP_TRY(hipMemcpyAsync(slow.data(), ctx->csv_slow.p, slow.size() * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  const auto t3 = csv_clock::now();
+  *tokens = h[0];
+  ctx->csv_last_slow = h[1];
+  ctx->csv_phase_s[0] = csv_secs(t0, t1);
+  ctx->csv_phase_s[1] = csv_secs(t1, t2);
+  ctx->csv_phase_s[2] = csv_secs(t2, t3);
+  return KNN_OK;
+}
+
+// atof / atoi of slow token (c, p), as the reference runs them: on a
+// NUL-terminated copy of the token, whose start is found backwards from its
+// terminator p.  Returns the fp64 bits or the int32 value.
+int64_t csv_slow_value(const char* text, int64_t p, bool is_label, std::string& tok) {
+  int64_t b = p;
+  while (b > 0 && text[b - 1] != ',' && text[b - 1] != '\n') --b;
+  tok.assign(text + b, text + p);
+  if (is_label) return (int64_t)atoi(tok.c_str());
+  const double v = atof(tok.c_str());
+  int64_t bits;
+  memcpy(&bits, &v, sizeof bits);
+  return bits;
+}
+
+int csv_check_read_args(const char* path, int dim, int64_t rows, const void* data,
+                        bool with_label, const void* labels, const int64_t* tokens) {
+  if (!path) return knn_fail(KNN_ERR_ARG, "null path");
+  if (dim < 1) return knn_fail(KNN_ERR_ARG, "dim must be >= 1");
+  if (rows < 0) return knn_fail(KNN_ERR_ARG, "rows must be >= 0");
+  if (rows > 0 && !data) return knn_fail(KNN_ERR_ARG, "null data");
+  if (with_label && rows > 0 && !labels) return knn_fail(KNN_ERR_ARG, "null labels (with_label)");
+  if (!tokens) return knn_fail(KNN_ERR_ARG, "null tokens");
+  return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int knn_csv_parse_device(knn_ctx* ctx, const char* d_text, int64_t bytes, int32_t dim,
+                         int32_t with_label, int64_t rows, double* d_data, int32_t* d_labels,
+                         int64_t* d_tokens, int64_t* d_slow, int64_t slow_cap, int64_t* d_nslow,
+                         void* stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (dim < 1) return knn_fail(KNN_ERR_ARG, "dim must be >= 1");
+  if (rows < 0) return knn_fail(KNN_ERR_ARG, "rows must be >= 0");
+  if (bytes < 0) return knn_fail(KNN_ERR_ARG, "bytes must be >= 0");
+  if (bytes > 0 && !d_text) return knn_fail(KNN_ERR_ARG, "null d_text");
+  if ((uintptr_t)d_text & 15) return knn_fail(KNN_ERR_ARG, "d_text must be 16-byte aligned");
+  if (rows > 0 && !d_data) return knn_fail(KNN_ERR_ARG, "null d_data");
+  if (with_label && rows > 0 && !d_labels)
+    return knn_fail(KNN_ERR_ARG, "null d_labels (with_label)");
+  if (!d_tokens || !d_nslow) return knn_fail(KNN_ERR_ARG, "null d_tokens / d_nslow");
+  if (slow_cap < 0 || (slow_cap > 0 && !d_slow))
+    return knn_fail(KNN_ERR_ARG, "bad slow list (slow_cap < 0, or null d_slow)");
+  int64_t cap;
+  if ((rc = csv_token_cap(dim, with_label != 0, rows, &cap))) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return csv_enqueue(ctx, d_text, bytes, dim, with_label != 0, cap, d_data, d_labels, d_tokens,
+                     d_slow, slow_cap, d_nslow, false, s);
+}
+
+int knn_csv_read(knn_ctx* ctx, const char* path, int32_t dim, int32_t with_label, int64_t rows,
+                 double* data, int32_t* labels, int64_t* tokens) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = csv_check_read_args(path, dim, rows, data, with_label != 0, labels, tokens))) return rc;
+  const bool wl = with_label != 0;
+  int64_t cap;
+  if ((rc = csv_token_cap(dim, wl, rows, &cap))) return rc;
+  if ((rc = ctx->csv_data.ensure((size_t)rows * dim * sizeof(double)))) return rc;
+  if ((rc = ctx->csv_lab.ensure((size_t)rows * sizeof(int32_t)))) return rc;
+  std::unique_ptr<char[]> buf;
+  std::vector<int64_t> slow;
+  int64_t bytes = 0;
+  if ((rc = csv_read_core(ctx, path, dim, wl, rows, cap, (double*)ctx->csv_data.p,
+                          (int32_t*)ctx->csv_lab.p, buf, &bytes, slow, tokens)))
+    return rc;
+  // the cells tokens reached are a prefix of each array; the rest stays as it was
+  const auto t3 = csv_clock::now();
+  hipStream_t s = ctx->stream;
+  const int64_t stored = std::min(*tokens, cap);
+  const int64_t nlab = wl ? (stored + dim) / ((int64_t)dim + 1) : 0;
+  const int64_t ndata = stored - nlab;
+  if (ndata > 0)
+    HIP_TRY(hipMemcpyAsync(data, ctx->csv_data.p, (size_t)ndata * sizeof(double),
+                           hipMemcpyDeviceToHost, s));
+  if (nlab > 0)
+    HIP_TRY(hipMemcpyAsync(labels, ctx->csv_lab.p, (size_t)nlab * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const auto t4 = csv_clock::now();
+  std::string tok;
+  for (size_t i = 0; i + 1 < slow.size(); i += 2) {
+    const int64_t c = slow[i], p = slow[i + 1];
+    if (c < 0 || c >= cap || p < 0 || p > bytes) continue;
+    const int64_t row = wl ? c / ((int64_t)dim + 1) : 0;
+    const bool is_label = wl && c - row * ((int64_t)dim + 1) == 0;
+    const int64_t v = csv_slow_value(buf.get(), p, is_label, tok);
+    if (is_label)
+      labels[row] = (int32_t)v;
+    else
+      memcpy(&data[wl ? c - row - 1 : c], &v, sizeof v);
+  }
+  ctx->csv_phase_s[3] = csv_secs(t3, t4);
+  ctx->csv_phase_s[4] = csv_secs(t4, csv_clock::now());
+  return KNN_OK;
+}
+
+int knn_csv_read_device(knn_ctx* ctx, const char* path, int32_t dim, int32_t with_label,
+                        int64_t rows, double* d_data, int32_t* d_labels, int64_t* tokens) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = csv_check_read_args(path, dim, rows, d_data, with_label != 0, d_labels, tokens)))
+    return rc;
+  const bool wl = with_label != 0;
+  int64_t cap;
+  if ((rc = csv_token_cap(dim, wl, rows, &cap))) return rc;
+  std::unique_ptr<char[]> buf;
+  std::vector<int64_t> slow;
+  int64_t bytes = 0;
+  if ((rc = csv_read_core(ctx, path, dim, wl, rows, cap, d_data, d_labels, buf, &bytes, slow,
+                          tokens)))
+    return rc;
+  const auto t4 = csv_clock::now();
+  std::string tok;
+  for (size_t i = 0; i + 1 < slow.size(); i += 2) {  // (c, p) -> (c, value)
+    const int64_t c = slow[i], p = slow[i + 1];
+    if (c < 0 || c >= cap || p < 0 || p > bytes) {
+      slow[i] = -1;
+      continue;
+    }
+    const bool is_label = wl && c % ((int64_t)dim + 1) == 0;
+    slow[i + 1] = csv_slow_value(buf.get(), p, is_label, tok);
+  }
+  if (!slow.empty()) {
+    hipStream_t s = ctx->stream;
+    if ((rc = ctx->csv_fix.ensure(slow.size() * sizeof(int64_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->csv_fix.p, slow.data(), slow.size() * sizeof(int64_t),
+                           hipMemcpyHostToDevice, s));
+    launch_csv_scatter((const int64_t*)ctx->csv_fix.p, (int64_t)(slow.size() / 2), dim, wl, cap,
+                       d_data, d_labels, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  ctx->csv_phase_s[4] = csv_secs(t4, csv_clock::now());
+  return KNN_OK;
+}
+
+int64_t knn_csv_last_slow(knn_ctx* ctx) { return ctx ? ctx->csv_last_slow : -1; }
+
+int knn_csv_last_phases(knn_ctx* ctx, double out_s[5]) {
+  if (!ctx || !out_s) return knn_fail(KNN_ERR_ARG, "null context / output");
+  for (int i = 0; i < 5; i++) out_s[i] = ctx->csv_phase_s[i];
   return KNN_OK;
 }
 

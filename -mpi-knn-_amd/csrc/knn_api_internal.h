@@ -117,6 +117,13 @@ struct knn_ctx {
   DevBuf o_lab, o_idx, o_dist, o_flags;
   // normalisation: per-thread partial max/min, bounds, host-API staging
   DevBuf nrm_part, nrm_mm, nrm_X;
+  // CSV reader: the conversion table (uploaded once), block counts and bases,
+  // and the file entry points' staging: text, values, labels, slow list,
+  // {tokens, slow count}, the host's (index, value) list
+  DevBuf csv_tab, csv_ws, csv_text, csv_data, csv_lab, csv_slow, csv_misc, csv_fix;
+  bool csv_tab_ready = false;
+  int64_t csv_last_slow = -1;                  // slow tokens of the last file call
+  double csv_phase_s[5] = {0, 0, 0, 0, 0};     // its read / h2d / parse / d2h / slow seconds
   std::vector<DevBuf*> all_bufs() {
     return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &XU, &i8_cent, &i8_gs,
             &XH,      &XT16,    &XS16,  &mu,      &mu_part, &Q64, &Q32,    &qvalid, &cand_v,   &cand_i,
@@ -126,7 +133,8 @@ struct knn_ctx {
             &ord_cent, &ord_cnorm, &ord_img, &ord_rank, &ord_rstart, &ord_perm, &ord_ipos, &ord_key, &ord_bcnt, &ord_tot,
             &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
             &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl,
-            &ev_lab, &ev_conf, &ev_unl};
+            &ev_lab, &ev_conf, &ev_unl, &csv_tab, &csv_ws, &csv_text, &csv_data, &csv_lab, &csv_slow,
+            &csv_misc, &csv_fix};
   }
 };
 

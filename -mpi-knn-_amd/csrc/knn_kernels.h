@@ -6,6 +6,10 @@
 
 #include "knn_dims.h"
 
+namespace knncsv {
+struct NumTable;  // knn_csv_num.h
+}
+
 namespace knnk {
 
 constexpr int kTR = 32;          // train rows per MFMA sub-tile of the resident kernel
@@ -543,5 +547,24 @@ void launch_minmax(const double* X, int64_t rows, int d, int64_t R, double* part
                    double* out_max, double* out_min, int init, hipStream_t s);
 void launch_normalize_apply(double* X, int64_t rows, int d, int64_t R, const double* vmax,
                             const double* vmin, hipStream_t s);
+
+// ---- CSV text -> fp64 rows / int32 labels (knn_csv.hip; the reference's
+// reader, cpp:154-222).  csv_block_count: workgroups of a file of `bytes` > 0
+// bytes = entries of cnt (uint32) and base (int64).  count + scan: terminators
+// per block, their exclusive scan and the file's token count (*tokens).
+// convert: every token c < cap converted (knn_csv_num.h) and stored by the
+// reference's rule, or appended as (c, terminator position) to slow [slow_cap]
+// [2] through the counter *nslow (zeroed by the caller; counts past slow_cap).
+// scatter: ent [n][2] = (c, fp64 bits or int32 label) written by the same rule.
+// text must be 16-byte aligned.
+int64_t csv_block_count(int64_t bytes);
+void launch_csv_count_scan(const char* text, int64_t bytes, unsigned int* cnt, int64_t* base,
+                           int64_t* tokens, hipStream_t s);
+void launch_csv_convert(const char* text, int64_t bytes, const int64_t* base,
+                        const knncsv::NumTable* tab, int dim, bool with_label, int64_t cap,
+                        double* data, int32_t* labels, int64_t* slow, int64_t slow_cap,
+                        int64_t* nslow, hipStream_t s);
+void launch_csv_scatter(const int64_t* ent, int64_t n, int dim, bool with_label, int64_t cap,
+                        double* data, int32_t* labels, hipStream_t s);
 
 }  // namespace knnk

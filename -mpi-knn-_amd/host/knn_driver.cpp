@@ -38,6 +38,13 @@
 // exact matches alone decide (KNN_VOTE_DISTANCE, knn_amd.h); it applies to the
 // validation pass, the test pass, --K_list, --loo and --confusion, and every
 // output keeps its format.
+// --csv host|gpu (default host): who parses the three CSV files.  host is the
+// multi-threaded reader of csv.cpp; gpu reads them through knn_csv_read on a
+// context of device 0 (the text is uploaded and converted by a kernel, the few
+// tokens it cannot certify by atof / atoi on the host): the same values bit
+// for bit, so stdout and Test_label.csv do not change.  With --timings the
+// "csv" line is followed by its parts (read, h2d, parse, d2h, slow) and the
+// number of slow tokens.
 // The timed region spans the same work as the reference (barrier to
 // barrier: CSV parsing, distribution, normalisation, both passes, output).
 #include <chrono>
@@ -76,6 +83,7 @@ struct Config {
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
   bool confusion = false;       // --confusion: print the selected K's confusion matrix
   int vote = KNN_VOTE_UNIFORM;  // --weights uniform|distance
+  bool csv_gpu = false;         // --csv gpu: the files are parsed on device 0
   std::vector<std::pair<std::string, long long>> tune;  // --tune KEY=VALUE (knn_set_tuning keys)
 };
 
@@ -88,7 +96,7 @@ void usage() {
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
           "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--confusion]\n"
-          "  [--tune KEY=VALUE]... [--weights uniform|distance]\n"
+          "  [--tune KEY=VALUE]... [--weights uniform|distance] [--csv host|gpu]\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
@@ -100,7 +108,8 @@ void usage() {
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
           "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
           "  (i8l1=2: also at 256 < dim <= 1024); --tune u16l1=1: the L1 pass on 16-bit\n"
-          "  fixed-point codes for any data at dim <= 256 (--Normalize true included)\n");
+          "  fixed-point codes for any data at dim <= 256 (--Normalize true included)\n"
+          "  --csv gpu parses the CSV files on GPU 0 (same values as the default host reader)\n");
 }
 
 // "1,3,5" -> {1, 3, 5}; false on an empty list, an empty item or a non-digit
@@ -169,6 +178,14 @@ int parse_args(int argc, char** argv, Config& c) {
         return 1;
       }
     }
+    else if (a == "csv") {
+      if (v == "host") c.csv_gpu = false;
+      else if (v == "gpu") c.csv_gpu = true;
+      else {
+        fprintf(stderr, "--csv takes host or gpu\n");
+        return 1;
+      }
+    }
     else if (a == "tune") {
       const size_t e = v.find('=');
       char* end = nullptr;
@@ -189,16 +206,35 @@ int parse_args(int argc, char** argv, Config& c) {
   exit(1);  // ≙ MPI_Abort(MPI_COMM_WORLD, 1)
 }
 
+// --csv gpu: the context the files are parsed on, the sums of their parts
+struct GpuCsv {
+  knn_ctx* ctx = nullptr;
+  double parts[5] = {0, 0, 0, 0, 0};  // read, h2d, parse, d2h, slow
+  int64_t slow = 0;
+};
+
 void load(const std::string& path, int dim, bool with_label, int64_t rows, std::vector<double>& X,
-          std::vector<int32_t>* lab, int threads) {
+          std::vector<int32_t>* lab, int threads, GpuCsv* gpu) {
   X.assign((size_t)rows * dim, 0.0);
   if (lab) lab->assign((size_t)rows, 0);
-  knnhost::CsvResult r =
-      knnhost::read_csv(path, dim, with_label, rows, X.data(), lab ? lab->data() : nullptr, threads);
-  if (!r.ok) die(r.error);
+  int64_t tokens = 0;
+  if (gpu) {
+    if (knn_csv_read(gpu->ctx, path.c_str(), dim, with_label, rows, X.data(),
+                     lab ? lab->data() : nullptr, &tokens))
+      die(knn_last_error());
+    double parts[5];
+    if (knn_csv_last_phases(gpu->ctx, parts)) die(knn_last_error());
+    for (int i = 0; i < 5; i++) gpu->parts[i] += parts[i];
+    gpu->slow += knn_csv_last_slow(gpu->ctx);
+  } else {
+    knnhost::CsvResult r = knnhost::read_csv(path, dim, with_label, rows, X.data(),
+                                             lab ? lab->data() : nullptr, threads);
+    if (!r.ok) die(r.error);
+    tokens = r.tokens;
+  }
   const int64_t want = rows * (dim + (with_label ? 1 : 0));
-  if (r.tokens != want)
-    die(path + ": expected " + std::to_string(want) + " values, found " + std::to_string(r.tokens));
+  if (tokens != want)
+    die(path + ": expected " + std::to_string(want) + " values, found " + std::to_string(tokens));
 }
 
 // "confusion K = <k>", the C x C matrix of list entry `sel` (conf: [nk][C][C]),
@@ -245,6 +281,9 @@ int main(int argc, char** argv) {
   for (const auto& kv : c.tune)
     if (knn_group_set_tuning(g, kv.first.c_str(), kv.second)) die(knn_last_error());
   if (knn_group_set_vote(g, c.vote)) die(knn_last_error());
+  GpuCsv gpu_csv;
+  if (c.csv_gpu && knn_create(&gpu_csv.ctx, 0)) die(knn_last_error());
+  GpuCsv* gc = c.csv_gpu ? &gpu_csv : nullptr;
 
   using clk = std::chrono::steady_clock;
   const auto start = clk::now();  // ≙ MPI_Barrier + MPI_Wtime, cpp:133-134
@@ -259,10 +298,17 @@ int main(int argc, char** argv) {
 
   std::vector<double> Xtr, Xte, Xva;
   std::vector<int32_t> Ltr, Lva;
-  load(c.train_file, c.dim, true, c.N_train, Xtr, &Ltr, c.threads);
-  load(c.test_file, c.dim, false, c.N_test, Xte, nullptr, c.threads);
-  if (c.Validation) load(c.validation_file, c.dim, true, c.N_val, Xva, &Lva, c.threads);
+  load(c.train_file, c.dim, true, c.N_train, Xtr, &Ltr, c.threads, gc);
+  load(c.test_file, c.dim, false, c.N_test, Xte, nullptr, c.threads, gc);
+  if (c.Validation) load(c.validation_file, c.dim, true, c.N_val, Xva, &Lva, c.threads, gc);
   phase("csv");
+  if (gc && c.timings) {
+    static const char* const names[5] = {"read", "h2d", "parse", "d2h", "slow"};
+    for (int i = 0; i < 5; i++)
+      fprintf(stderr, "[knn_mpi_amd]   csv.%-6s %.3f s\n", names[i], gc->parts[i]);
+    fprintf(stderr, "[knn_mpi_amd]   csv slow tokens %lld\n", (long long)gc->slow);
+  }
+  if (gc) mark = clk::now();  // (the lines above are not part of the next phase)
 
   if (c.Normalize) {  // cpp:229-306 on the GPUs: sharded min/max + RCCL all-reduce + apply
     std::vector<double*> sets{Xtr.data(), Xte.data()};
@@ -369,6 +415,7 @@ int main(int argc, char** argv) {
 
   const auto finish = clk::now();  // cpp:395-396
   knn_group_destroy(g);
+  if (gpu_csv.ctx) knn_destroy(gpu_csv.ctx);
   std::cout << "Running time is " << std::chrono::duration<double>(finish - start).count()
             << " second" << std::endl;
   return 0;

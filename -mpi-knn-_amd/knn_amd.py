@@ -47,7 +47,11 @@ EXPORTED = (
     "knn_group_classify_sweep_eval", "knn_group_loo_sweep_eval",
     "knn_set_vote", "knn_get_vote", "knn_group_set_vote", "knn_vote_sweep_weighted_device",
     "knn_vote_weights_device",
+    "knn_csv_parse_device", "knn_csv_read", "knn_csv_read_device", "knn_csv_last_slow",
+    "knn_csv_last_phases",
 )
+# bytes of CSV text one workgroup of knn_csv_parse_device owns (knn_amd.h)
+CSV_BLOCK_BYTES = 16384
 # knn_confusion_device keeps its histograms in LDS per wave up to CONF_SMALL_C
 # classes, per workgroup up to CONF_LDS_C, and counts with global atomics
 # beyond; knn_vote_counts_device keeps LDS counters up to COUNTS_LDS_C classes
@@ -173,6 +177,11 @@ def lib():
         "knn_vote_sweep_weighted_device": ([P, P, P, i64, i32, P, i64, P, i32, P, P, P, P],
                                            ctypes.c_int),
         "knn_vote_weights_device": ([P, P, P, i64, i32, P, i64, i32, i32, P, P], ctypes.c_int),
+        "knn_csv_parse_device": ([P, P, i64, i32, i32, i64, P, P, P, P, i64, P, P], ctypes.c_int),
+        "knn_csv_read": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
+        "knn_csv_read_device": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
+        "knn_csv_last_slow": ([P], i64),
+        "knn_csv_last_phases": ([P, ctypes.POINTER(f64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -683,6 +692,49 @@ class Classifier:
     def normalize_device(self, dX_ptr, rows, d, d_max, d_min, stream=None):
         _check(lib().knn_normalize_device(self._h, dX_ptr, int(rows), int(d), d_max, d_min,
                                           stream))
+
+    def read_csv(self, path, dim, with_label, rows, device=False):
+        """One of the reference's CSV files (cpp:154-222) parsed on the GPU:
+        (data [rows, dim] float64, labels [rows] int32 or None, tokens found),
+        bit for bit what the reference's reader leaves in zeroed arrays.
+        device=False: numpy arrays; device=True: torch tensors on the context's
+        GPU (zero-initialised), ready for set_train_device / normalize_device /
+        classify_device."""
+        tokens = ctypes.c_int64(0)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            data = torch.zeros((int(rows), int(dim)), dtype=torch.float64, device=dev)
+            labels = torch.zeros(int(rows), dtype=torch.int32, device=dev) if with_label else None
+            torch.cuda.synchronize(dev)  # the zeros, whichever stream made them
+            _check(lib().knn_csv_read_device(
+                self._h, os.fsencode(path), int(dim), int(bool(with_label)), int(rows),
+                data.data_ptr() or None, labels.data_ptr() or None if with_label else None,
+                ctypes.byref(tokens)))
+        else:
+            data = np.zeros((int(rows), int(dim)), np.float64)
+            labels = np.zeros(int(rows), np.int32) if with_label else None
+            _check(lib().knn_csv_read(self._h, os.fsencode(path), int(dim),
+                                      int(bool(with_label)), int(rows), _ptr(data), _ptr(labels),
+                                      ctypes.byref(tokens)))
+        return data, labels, tokens.value
+
+    def csv_parse_device(self, d_text, nbytes, dim, with_label, rows, d_data, d_labels, d_tokens,
+                         d_slow, slow_cap, d_nslow, stream=None):
+        """knn_csv_parse_device: device pointers, enqueue only (knn_amd.h)."""
+        _check(lib().knn_csv_parse_device(self._h, d_text, int(nbytes), int(dim),
+                                          int(bool(with_label)), int(rows), d_data, d_labels,
+                                          d_tokens, d_slow, int(slow_cap), d_nslow, stream))
+
+    def csv_last_slow(self):
+        """Slow tokens (converted by the host's atof / atoi) of the last read_csv."""
+        return lib().knn_csv_last_slow(self._h)
+
+    def csv_last_phases(self):
+        """Seconds of the last read_csv: read, h2d, parse, d2h, slow."""
+        out = (ctypes.c_double * 5)()
+        _check(lib().knn_csv_last_phases(self._h, out))
+        return dict(zip(("read", "h2d", "parse", "d2h", "slow"), out))
 
 
 class Group:

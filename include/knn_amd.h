@@ -66,6 +66,9 @@ extern "C" {
 #define KNN_ERR_NOMEM -4   /* device allocation failed */
 #define KNN_ERR_COMM -5    /* RCCL failure */
 
+/* bytes of CSV text one workgroup of the reader owns (knn_csv_parse_device) */
+#define KNN_CSV_BLOCK_BYTES 16384
+
 #define KNN_METRIC_L2 0 /* Euclidean_distance = true  (cpp:114, 320, 363) */
 #define KNN_METRIC_L1 1 /* Euclidean_distance = false (cpp:114, 321, 364) */
 
@@ -427,6 +430,73 @@ int knn_normalize_device(knn_ctx* ctx, double* d_X, int64_t rows, int32_t d,
                          const double* d_max, const double* d_min, void* stream);
 int knn_normalize(knn_ctx* ctx, double* const* sets, const int64_t* rows, int32_t nsets,
                   int32_t d, double* out_max, double* out_min);
+
+/* ---- the reference's CSV reader on the GPU (replaces cpp:154-222) ---------
+ * Values equal the reference reader's, bit for bit, for every file: data
+ * tokens are atof's fp64 values, label tokens atoi's.
+ * Token rule (getline on '\n', then on ','; one running token counter c over
+ * the whole file, rows come from the count, not from line breaks): position p
+ * TERMINATES a token iff text[p] == ',', or text[p] == '\n' (or p == bytes,
+ * the end of the file) and p > 0 and text[p-1] is neither ',' nor '\n'; the
+ * token begins after the previous ',' or '\n', or at 0.  So every segment
+ * followed by a comma is a token (possibly empty), a line's last segment only
+ * if it is non-empty.  with_label: token c with c % (dim+1) == 0 is
+ * labels[c / (dim+1)], any other token data[c - c/(dim+1) - 1]; without
+ * labels token c is data[c].  Tokens at c >= rows * (dim [+ 1]) are counted
+ * and not stored; cells no token reaches are NOT written (they keep what the
+ * caller put there).
+ * Conversion tiers.  A device kernel converts every token it can prove
+ * correctly rounded: the whole token must match -? D* (. D*)? ([eE] [+-]? D+)?
+ * with at least one mantissa digit, at most 19 significant digits and at most
+ * 64 bytes; with w its decimal significand and q its decimal exponent, w == 0
+ * gives +-0.0, tier 1 (Clinger: w < 2^53, |q| <= 22) is one correctly rounded
+ * fp64 multiply or divide of two exact operands, tier 2 (Eisel-Lemire: any
+ * other w < 2^64, -342 <= q <= 308) multiplies by a 128-bit truncated power of
+ * five and gives up where the truncation could decide the rounding, on
+ * subnormal results and on overflow.  Labels: the whole token -? D{1,9}.
+ * Every other token -- blanks, '+', a trailing '\r', hex, inf / nan, garbage,
+ * the empty token -- is SLOW: the host runs atof / atoi itself on a
+ * NUL-terminated copy (knn_csv_read*), or the caller does
+ * (knn_csv_parse_device).
+ *
+ * knn_csv_parse_device: the building block.  d_text [bytes] is the file's
+ * text on the device (16-byte aligned).  Enqueues three steps on `on_stream` (a
+ * hipStream_t, NULL = the context's stream, like every _device call): the
+ * terminators of every KNN_CSV_BLOCK_BYTES block, their exclusive scan, the
+ * conversion; it returns without waiting.  d_data [rows*dim] (fp64), d_labels
+ * [rows] (required iff with_label), *d_tokens = the file's token count,
+ * *d_nslow = the number of slow tokens among the stored ones, d_slow
+ * [slow_cap][2] = (c, p) of each: its token index and its terminator's
+ * position, in no particular order.  d_nslow keeps counting past slow_cap;
+ * entries beyond it are dropped (call again with a larger list).  bytes == 0
+ * launches nothing and reports 0 tokens.  KNN_ERR_ARG for dim < 1, rows < 0 or
+ * bytes < 0.  Needs no train set. */
+int knn_csv_parse_device(knn_ctx* ctx, const char* d_text, int64_t bytes, int32_t dim,
+                         int32_t with_label, int64_t rows, double* d_data, int32_t* d_labels,
+                         int64_t* d_tokens, int64_t* d_slow, int64_t slow_cap, int64_t* d_nslow,
+                         void* on_stream);
+/* A CSV file into host arrays data [rows*dim] and labels [rows] (required iff
+ * with_label), *tokens = the tokens found; waits for the result.  Reads the
+ * file (parallel pread, at most 16 threads), uploads the text, parses it
+ * (token rule and tiers above), copies the values back and converts the slow
+ * tokens with atof / atoi: the arrays hold exactly what the reference reader
+ * leaves in them.  The slow list starts at max(4096, bytes / 64) entries; when
+ * more tokens are slow the conversion runs once more with room for all.  A
+ * missing or unreadable file is KNN_ERR_ARG with the path in the message. */
+int knn_csv_read(knn_ctx* ctx, const char* path, int32_t dim, int32_t with_label, int64_t rows,
+                 double* data, int32_t* labels, int64_t* tokens);
+/* The same with the values left on the device (d_data, d_labels: device
+ * pointers on the context's GPU; same token rule, tiers and values): the slow
+ * tokens' host values go up as an (index, value) list that a small kernel
+ * scatters.  Runs on the context's stream; complete on return. */
+int knn_csv_read_device(knn_ctx* ctx, const char* path, int32_t dim, int32_t with_label,
+                        int64_t rows, double* d_data, int32_t* d_labels, int64_t* tokens);
+/* Slow tokens of the last knn_csv_read / knn_csv_read_device (-1: none yet). */
+int64_t knn_csv_last_slow(knn_ctx* ctx);
+/* Host seconds of that call's parts: out_s[0] reading the file, [1] text to
+ * the device, [2] the kernels and the slow list's way back, [3] values to the
+ * host (0 for knn_csv_read_device), [4] the slow tokens' conversion. */
+int knn_csv_last_phases(knn_ctx* ctx, double out_s[5]);
 
 /* Per-phase device timing with HIP events recorded on the stream the
  * kernels run on (off by default).  Phases: 0 = query prep, 1 = candidate
