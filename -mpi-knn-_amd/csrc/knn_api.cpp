@@ -254,6 +254,8 @@ static int build_train(knn_ctx* ctx, const double* dX, const int32_t* dlab, int6
     return knn_fail(KNN_ERR_ARG, "dimension " + std::to_string(d) + " not supported by this build");
   const int64_t n_pad = (n + kRowAlign - 1) / kRowAlign * kRowAlign;
   int rc;
+  ctx->groups = nullptr;  // group ids belong to one train set (knn_set_groups)
+  ctx->n_groups = ctx->gmax = 0;
   // padded rows [payload | seeds] (+1 KiB slack: the last LDS-DMA piece of
   // the last tile may read past the final row)
   if ((rc = ctx->X32.ensure((size_t)n_pad * (DP + 4) * sizeof(float) + 1024))) return rc;
@@ -1118,6 +1120,118 @@ int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* k
                     d_correct, d_conf, d_unl, zero, s);
 }
 
+// ---- K sweep under group exclusion / leave-group-out (knn_lgo.hip)
+
+// knn_classify_sweep_gexcl_device's body on stream s (d_qgroup non-null)
+static int gexcl_sweep(knn_ctx* ctx, const double* dQ, int64_t m, const int32_t* d_qgroup,
+                       const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
+                       const int32_t* d_truth, int64_t* d_correct, int64_t* d_idx, double* d_dist,
+                       int32_t* d_flags, hipStream_t s) {
+  int rc;
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  if (!ctx->groups)
+    return knn_fail(KNN_ERR_STATE, "sweep under group exclusion before knn_set_groups");
+  const TrainDev& t = ctx->train;
+  const int gmax = ctx->gmax;
+  int32_t kmax = 0;
+  // a whole group (at most gmax rows) may be taken out
+  if ((rc = knn_sweep_check_ks(ks, nk, t.n - gmax, &kmax))) return rc;
+  if (kmax == 0)  // every K is 0: no neighbour is read
+    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
+                                     d_idx, d_dist, d_flags, s);
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const int* dks = (const int*)ctx->sw_ks.p;
+  // one search at kmax + gmax into internal rows (neither queues ties nor runs
+  // the reference-order pass), compacted into the caller's kmax-entry rows
+  const int k1 = kmax + gmax;  // <= n
+  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->loo_idx.ensure((size_t)m * k1 * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->loo_dist.ensure((size_t)m * k1 * sizeof(double)))) return rc;
+  if ((rc = ctx->loo_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
+  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
+  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  Sink sink{};
+  sink.mode = MODE_SINGLE;
+  sink.k = k1;
+  sink.idx_off = ctx->idx_off;
+  sink.labels = (int32_t*)ctx->sw_lab.p;
+  sink.idx = (int64_t*)ctx->loo_idx.p;
+  sink.dist = (double*)ctx->loo_dist.p;
+  sink.flags = (int32_t*)ctx->loo_flags.p;
+  sink.tie_defer = 1;
+  const int W = (int)std::min<int64_t>((int64_t)k1 + 1, t.n);
+  rc = k1 > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
+                  : knn_run_search(ctx, dQ, m, W, metric, sink, s);
+  if (rc) return rc;
+  Sink out = sink;  // the rows of the reduced sets, at kmax
+  out.k = kmax;
+  out.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
+  out.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
+  out.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
+  launch_lgo_drop(sink.dist, sink.idx, sink.flags, d_qgroup, ctx->groups, m, kmax, k1, t.lab,
+                  ctx->idx_off, t.n, out.dist, out.idx, out.flags, ctx->cu_count, s);
+  if (ctx->tune.ties) {  // the sweep's tie scan; std::sort over each query's remaining records
+    out.tie_mode = ctx->tune.ties;
+    TieScratch ts;
+    if ((rc = tie_setup(ctx, m, out, ts, true, s))) return rc;
+    launch_sweep_tie_scan(out.dist, out.idx, out.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
+                          out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
+    launch_tie_order_group(metric, t, dQ, out.tie_q, out.tie_cnt, ctx->class_cnt,
+                           (unsigned char*)ctx->tie_ws.p, ts.per, ts.nwg, out,
+                           (unsigned long long*)ctx->totals.p + 2, s, d_qgroup, ctx->groups);
+  }
+  sweep_votes(ctx, out.idx, out.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+  return KNN_OK;
+}
+
+// leave-group-out over train rows [row0, row0 + rows): the rows are the
+// queries, each excludes its own group and its own label is its truth
+int knn_lgo_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                 int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                 double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl, bool zero,
+                 hipStream_t s) {
+  int rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before set_train");
+  if (!ctx->groups) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before knn_set_groups");
+  const TrainDev& t = ctx->train;
+  if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
+    return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
+                                     std::to_string(row0) + " + " + std::to_string(rows) +
+                                     ") outside the train set [0, " + std::to_string(t.n) + ")");
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  if (nk >= 1 && nk <= 4096) {  // (a bad nk is reported by the sweep's own check)
+    if (zero && d_conf) HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)nk * cc * sizeof(int64_t), s));
+    if (zero && d_unl) HIP_TRY(hipMemsetAsync(d_unl, 0, (size_t)nk * sizeof(int64_t), s));
+  }
+  int32_t* L = d_labels;
+  if (!L) {
+    if (!d_conf && !d_unl) return knn_fail(KNN_ERR_ARG, "null labels output");
+    const size_t cells = (size_t)std::max<int64_t>(rows, 1) * (size_t)std::max(nk, 1);
+    if ((rc = ctx->ev_lab.ensure(cells * sizeof(int32_t)))) return rc;
+    L = (int32_t*)ctx->ev_lab.p;
+  }
+  if ((rc = ctx->lgo_qg.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int32_t)))) return rc;
+  int32_t* qg = (int32_t*)ctx->lgo_qg.p;
+  launch_lgo_self(qg, ctx->groups, rows, row0, s);  // query i is train row row0 + i
+  HIP_TRY(hipGetLastError());
+  rc = gexcl_sweep(ctx, t.X64 + row0 * t.d, rows, qg, ks, nk, metric, L,
+                   d_correct ? t.lab + row0 : nullptr, d_correct, d_idx, d_dist, d_flags, s);
+  if (rc || rows == 0 || (!d_conf && !d_unl)) return rc;
+  launch_eval_confusion(L, nk, rows, t.lab + row0, ctx->class_cnt, (unsigned long long*)d_conf,
+                        (unsigned long long*)d_unl, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the confusion pass
+  return KNN_OK;
+}
+
 extern "C" {
 
 int knn_classify_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t k, int32_t metric,
@@ -1481,6 +1595,161 @@ int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, i
       HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
                              (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
   }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_correct)
+    for (int32_t j = 0; j < nk; j++) {
+      out_correct[j] = 0;
+      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
+    }
+  return KNN_OK;
+}
+
+// ---- K sweep under group exclusion / leave-group-out (knn_lgo.hip)
+
+// attaches device-resident group ids to the current train set: the range
+// check and the group-size histogram run on the device, the call waits for
+// {first bad row, gmax} as set_train waits for its checks
+static int attach_groups(knn_ctx* ctx, const int32_t* d_groups, int32_t n_groups) {
+  int rc;
+  const int64_t n = ctx->train.n;
+  ctx->groups = nullptr;
+  ctx->n_groups = ctx->gmax = 0;
+  if (n_groups <= 0) return knn_fail(KNN_ERR_ARG, "n_groups must be > 0");
+  if ((rc = ctx->grp_hist.ensure((size_t)n_groups * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->grp_stat.ensure(2 * sizeof(unsigned long long)))) return rc;
+  hipStream_t s = ctx->stream;
+  unsigned long long h[2] = {(unsigned long long)n, 0};  // first bad row (n: none) | gmax
+  HIP_TRY(hipMemsetAsync(ctx->grp_hist.p, 0, (size_t)n_groups * sizeof(int32_t), s));
+  HIP_TRY(hipMemcpyAsync(ctx->grp_stat.p, h, sizeof(h), hipMemcpyHostToDevice, s));
+  launch_lgo_group_stats(d_groups, n, n_groups, (int32_t*)ctx->grp_hist.p,
+                         (unsigned long long*)ctx->grp_stat.p,
+                         (int32_t*)((unsigned long long*)ctx->grp_stat.p + 1), ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, ctx->grp_stat.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h[0] < (unsigned long long)n)
+    return knn_fail(KNN_ERR_ARG, "group id out of [0, n_groups) at row " + std::to_string(h[0]));
+  ctx->groups = d_groups;
+  ctx->n_groups = n_groups;
+  ctx->gmax = (int32_t)(h[1] & 0xffffffffu);
+  return KNN_OK;
+}
+
+int knn_set_groups_device(knn_ctx* ctx, const int32_t* d_groups, int32_t n_groups) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "set_groups before set_train");
+  if (!d_groups) {  // clears the groups
+    ctx->groups = nullptr;
+    ctx->n_groups = ctx->gmax = 0;
+    return KNN_OK;
+  }
+  return attach_groups(ctx, d_groups, n_groups);
+}
+
+int knn_set_groups(knn_ctx* ctx, const int32_t* groups, int32_t n_groups) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "set_groups before set_train");
+  if (!groups) return knn_set_groups_device(ctx, nullptr, 0);
+  const int64_t n = ctx->train.n;
+  ctx->groups = nullptr;  // (the copy below overwrites the ids the last call attached)
+  ctx->n_groups = ctx->gmax = 0;
+  if ((rc = ctx->grp_own.ensure((size_t)n * sizeof(int32_t)))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->grp_own.p, groups, (size_t)n * sizeof(int32_t),
+                         hipMemcpyHostToDevice, ctx->stream));
+  return attach_groups(ctx, (const int32_t*)ctx->grp_own.p, n_groups);
+}
+
+int32_t knn_get_group_max(knn_ctx* ctx) { return ctx && ctx->groups ? ctx->gmax : 0; }
+
+int knn_classify_sweep_gexcl_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                    const int32_t* d_qgroup, const int32_t* ks, int32_t nk,
+                                    int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                    int64_t* d_correct, int64_t* d_idx, double* d_dist,
+                                    int32_t* d_flags, void* on_stream) {
+  if (!d_qgroup)  // nothing excluded for any query: the plain sweep
+    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
+                                     d_idx, d_dist, d_flags, on_stream);
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  hipStream_t s = on_stream ? (hipStream_t)on_stream : ctx->stream;
+  return gexcl_sweep(ctx, dQ, m, d_qgroup, ks, nk, metric, d_labels, d_truth, d_correct, d_idx,
+                     d_dist, d_flags, s);
+}
+
+int knn_lgo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                         int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                         double* d_dist, int32_t* d_flags, void* on_stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  hipStream_t s = on_stream ? (hipStream_t)on_stream : ctx->stream;
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  return knn_lgo_rows(ctx, row0, rows, ks, nk, metric, d_labels, d_correct, d_idx, d_dist, d_flags,
+                      nullptr, nullptr, true, s);
+}
+
+int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
+                  int64_t* out_correct, int64_t* out_conf, int64_t* out_unl, int64_t* out_idx,
+                  double* out_dist, int32_t* out_flags) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
+  if (!ctx->groups) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before knn_set_groups");
+  const int64_t n = ctx->train.n;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, n - ctx->gmax, &kmax))) return rc;
+  if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
+  // fixed batches: the workspace does not grow with n
+  const int64_t B = std::min<int64_t>(n, 16384);
+  const int64_t nb = (n + B - 1) / B;
+  const size_t bk = (size_t)B * std::max(kmax, 1);
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
+  if (out_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
+  hipStream_t s = ctx->stream;
+  // conf / unl are summed over the batches on the device, correct on the host
+  if (out_conf) HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+  if (out_unl) HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
+  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);  // per batch, summed at the end
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t r0 = b * B, rows = std::min(B, n - r0);
+    rc = knn_lgo_rows(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
+                      out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
+                      out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
+                      out_dist ? (double*)ctx->o_dist.p : nullptr, (int32_t*)ctx->o_flags.p,
+                      out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
+                      out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, false, s);
+    if (rc) return rc;
+    // the batch's labels [nk][rows] -> columns [r0, r0 + rows) of [nk][n]
+    if (out_labels)
+      HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
+                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                               (size_t)nk, hipMemcpyDeviceToHost, s));
+    if (out_correct)
+      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, s));
+    if (out_flags)
+      HIP_TRY(hipMemcpyAsync(out_flags + r0, ctx->o_flags.p, (size_t)rows * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, s));
+    if (out_idx && kmax > 0)
+      HIP_TRY(hipMemcpyAsync(out_idx + r0 * kmax, ctx->o_idx.p,
+                             (size_t)rows * kmax * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (out_dist && kmax > 0)
+      HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
+                             (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (out_conf)
+    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+  if (out_unl)
+    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (out_correct)
     for (int32_t j = 0; j < nk; j++) {

@@ -110,6 +110,13 @@ struct knn_ctx {
   // K sweep under exclusion: the search's rows / flags at kmax + 1, the
   // exclusions of a leave-one-out batch (and the host twin's staging)
   DevBuf loo_idx, loo_dist, loo_flags, loo_excl;
+  // K sweep under group exclusion (knn_set_groups): the train rows' group ids
+  // (own copy or the caller's device array; null = none set), their count and
+  // the largest group's size; the host variant's copy, the histogram and
+  // {first bad row, gmax} of the check, the groups of a leave-group-out batch
+  const int32_t* groups = nullptr;
+  int32_t n_groups = 0, gmax = 0;
+  DevBuf grp_own, grp_hist, grp_stat, lgo_qg;
   // per-class evaluation: the sweep's labels [nk][m] when the caller wants
   // none, host-API staging of conf [nk][C][C] and unl [nk]
   DevBuf ev_lab, ev_conf, ev_unl;
@@ -133,6 +140,7 @@ struct knn_ctx {
             &ord_cent, &ord_cnorm, &ord_img, &ord_rank, &ord_rstart, &ord_perm, &ord_ipos, &ord_key, &ord_bcnt, &ord_tot,
             &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
             &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl,
+            &grp_own, &grp_hist, &grp_stat, &lgo_qg,
             &ev_lab, &ev_conf, &ev_unl, &csv_tab, &csv_ws, &csv_text, &csv_data, &csv_lab, &csv_slow,
             &csv_misc, &csv_fix};
   }
@@ -148,5 +156,12 @@ int knn_sweep_check_ks(const int32_t* ks, int32_t nk, int64_t n, int32_t* kmax);
 int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
                       int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_conf,
                       int64_t* d_unl, bool zero, hipStream_t s);
+// Leave-group-out sweep over train rows [row0, row0 + rows) with the optional
+// evaluation (knn_lgo_sweep_device's body; d_conf / d_unl nullable): zero =
+// false ADDS into d_conf / d_unl, as knn_loo_eval_rows
+int knn_lgo_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                 int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                 double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl, bool zero,
+                 hipStream_t s);
 int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                    const knnk::Sink& sink, hipStream_t s);

@@ -1021,7 +1021,17 @@ int knn_group_classify_sweep_eval(knn_group* g, const double* Q, int64_t m, cons
 // rank sums conf / unl over its batches on its GPU, the host over the ranks.
 static int group_loo(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
                      int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
-                     int64_t* out_unl, bool eval) {
+                     int64_t* out_unl, bool eval, bool lgo = false) {
+  if (lgo) {  // leave-group-out (knn_group_lgo_sweep): the same walk under group exclusion
+    if (!g || !g->trained)
+      return knn_fail(KNN_ERR_STATE, "group leave-group-out sweep before set_train");
+    if (g->mode == 1)
+      return knn_fail(KNN_ERR_ARG,
+                      "the leave-group-out sweep is not served in the train-sharded mode (mode 1): "
+                      "use a query-sharded group (mode 0)");
+    if (!knn_get_group_max(g->ctx[0]))
+      return knn_fail(KNN_ERR_STATE, "group leave-group-out sweep before set_groups");
+  }
   if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group leave-one-out sweep before set_train");
   if (g->mode == 1)
     return knn_fail(KNN_ERR_ARG,
@@ -1035,7 +1045,8 @@ static int group_loo(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric
   const int64_t n = g->n;
   const size_t cc = (size_t)g->class_cnt * g->class_cnt;
   std::vector<std::vector<int64_t>> hconf(g->ndev), hunl(g->ndev);
-  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
+  if ((rc = knn_sweep_check_ks(ks, nk, lgo ? n - knn_get_group_max(g->ctx[0]) : n - 1, &kmax)))
+    return rc;
   const int G = g->ndev;
   const int64_t B = 16384;
   // per rank and batch: the correct counts, summed on the host at the end
@@ -1060,7 +1071,12 @@ static int group_loo(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric
     }
     for (int64_t b = 0; b < nb; b++) {
       const int64_t q0 = r0 + b * B, rows = std::min(B, r1 - q0);
-      if (eval)
+      if (lgo)
+        rc = knn_lgo_rows(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
+                          out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr, nullptr,
+                          nullptr, eval ? (int64_t*)g->sconf[i].p : nullptr,
+                          eval ? (int64_t*)g->sunl[i].p : nullptr, false, s);
+      else if (eval)
         rc = knn_loo_eval_rows(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
                                out_correct ? (int64_t*)g->scorr[i].p : nullptr,
                                (int64_t*)g->sconf[i].p, (int64_t*)g->sunl[i].p, false, s);
@@ -1123,6 +1139,24 @@ int knn_group_loo_sweep_eval(knn_group* g, const int32_t* ks, int32_t nk, int32_
                              int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
                              int64_t* out_unl) {
   return group_loo(g, ks, nk, metric, out_labels, out_correct, out_conf, out_unl, true);
+}
+
+int knn_group_set_groups(knn_group* g, const int32_t* groups, int32_t n_groups) {
+  if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group set_groups before set_train");
+  if (g->mode == 1)
+    return knn_fail(KNN_ERR_ARG,
+                    "group ids are not served in the train-sharded mode (mode 1): "
+                    "use a query-sharded group (mode 0)");
+  // every rank holds the whole train set and keeps its own copy of the ids
+  return for_each_dev(g, [&](int i) { return knn_set_groups(g->ctx[i], groups, n_groups); });
+}
+
+int knn_group_lgo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                        int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                        int64_t* out_unl) {
+  if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
+  return group_loo(g, ks, nk, metric, out_labels, out_correct, out_conf, out_unl,
+                   out_conf || out_unl, true);
 }
 
 double knn_group_last_compute_seconds(knn_group* g) { return g ? g->last_compute : -1.0; }

@@ -392,6 +392,31 @@ void launch_tie_order(int metric, const TrainDev& t, const double* Q64, const in
                       const int* tie_cnt, int class_cnt, unsigned char* scratch, int64_t per_wg,
                       int nwg, const Sink& sink, unsigned long long* totals, hipStream_t s,
                       const int64_t* excl = nullptr);
+// The same pass under group exclusion (knn_lgo.hip; a kernel of its own):
+// query q's std::sort runs over the records left, in row order, when every
+// train row r with groups[r] == qgroup[q] is taken out (groups [n], local
+// rows; a qgroup value that no row carries excludes nothing)
+void launch_tie_order_group(int metric, const TrainDev& t, const double* Q64, const int* tie_q,
+                            const int* tie_cnt, int class_cnt, unsigned char* scratch,
+                            int64_t per_wg, int nwg, const Sink& sink, unsigned long long* totals,
+                            hipStream_t s, const int32_t* qgroup, const int32_t* groups);
+// K sweep under group exclusion (knn_lgo.hip): compacts the search's rows at
+// k1 = kmax + gmax (in_dist / in_idx [m][k1], in_flags [m]) into [m][kmax] rows
+// without the train rows of group qgroup[q] (groups [n]: the id of every local
+// row, at most gmax rows per id) and the flags of a kmax search on the reduced
+// set, as launch_loo_drop.
+void launch_lgo_drop(const double* in_dist, const int64_t* in_idx, const int32_t* in_flags,
+                     const int32_t* qgroup, const int32_t* groups, int64_t m, int kmax, int k1,
+                     const int32_t* lab, int64_t idx_base, int64_t n, double* out_dist,
+                     int64_t* out_idx, int32_t* out_flags, int cus, hipStream_t s);
+// qgroup[i] = groups[row0 + i] (leave-one-group-out: query i is train row row0 + i)
+void launch_lgo_self(int32_t* qgroup, const int32_t* groups, int64_t rows, int64_t row0,
+                     hipStream_t s);
+// group sizes into hist [n_groups] (zeroed by the caller), the first row whose
+// id lies outside [0, n_groups) into *bad (preset to n by the caller) and the
+// largest group's size into *gmax (zeroed by the caller)
+void launch_lgo_group_stats(const int32_t* groups, int64_t n, int32_t n_groups, int32_t* hist,
+                            unsigned long long* bad, int32_t* gmax, int cus, hipStream_t s);
 // K sweep under exclusion (knn_loo.hip): compacts the search's rows at kmax + 1
 // (in_dist / in_idx [m][kmax + 1], in_flags [m]) into [m][kmax] rows without
 // train row excl[q] (global index; excl null or a value outside [idx_base,

@@ -1798,6 +1798,63 @@ tie_order_kernel(TrainDev t, const double* __restrict__ Q64, const int* __restri
   }
 }
 
+// K sweep under group exclusion (knn_lgo.hip): the reference's std::sort over
+// the n - c records left without the c rows of group qgroup[q], in row order.
+// Every row's distance goes to D[row]; the kept records are then compacted
+// stably: each thread counts the kept rows of its contiguous piece, one block
+// scan gives the pieces' first positions, and one ordered write puts the row
+// numbers into P and the distances (as two 32-bit halves: Lb / Rb are free
+// until the sort, and Lb is 8-byte aligned only for even n) into Lb / Rb, from
+// where they return to D[0, n - c).  A kernel of its own: tie_order_kernel
+// keeps its code.
+template <int METRIC>
+__global__ void __launch_bounds__(kTieThreads)
+tie_order_group_kernel(TrainDev t, const double* __restrict__ Q64, const int* __restrict__ tie_q,
+                       const int* __restrict__ tie_cnt, int class_cnt,
+                       unsigned char* __restrict__ scratch, int64_t per_wg, Sink sink,
+                       unsigned long long* totals, const int32_t* __restrict__ qgroup,
+                       const int32_t* __restrict__ groups) {
+  __shared__ double tiles[kTieThreads / 64][64 * (kFullDC + 1)];
+  __shared__ RefSortShared s;
+  const int count = *tie_cnt;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && totals && count)
+    atomicAdd(totals, (unsigned long long)count);  // running count of re-ordered queries
+  const int n = (int)t.n;
+  unsigned char* base = scratch + (int64_t)blockIdx.x * per_wg;
+  double* D = (double*)base;
+  int* P = (int*)(D + n);
+  int* Lb = P + n;
+  int* Rb = Lb + n;
+  int* cnt = Rb + n;
+  const int tid = threadIdx.x;
+  const int seg = (n + kTieThreads - 1) / kTieThreads;
+  const int a0 = (int)min((int64_t)n, (int64_t)tid * seg), a1 = (int)min((int64_t)n, (int64_t)a0 + seg);
+  for (int i = blockIdx.x; i < count; i += gridDim.x) {
+    const int64_t q = tie_q[i];
+    const int gq = qgroup[q];  // ids lie in [0, n_groups): any other value matches no row
+    exact_all_dist<METRIC>(t, Q64 + q * t.d, D, tiles[tid >> 6]);
+    int ck = 0;
+    for (int r = a0; r < a1; ++r) ck += groups[r] != gq;
+    int k_ex, z_in, nr, z_tot;
+    block_scan2(ck, 0, k_ex, z_in, nr, z_tot, s.sc);  // (its barriers order D's writes too)
+    for (int r = a0, w = k_ex; r < a1; ++r)
+      if (groups[r] != gq) {
+        const long long bits = __double_as_longlong(D[r]);
+        P[w] = r;
+        Lb[w] = (int)(bits >> 32);
+        Rb[w] = (int)bits;
+        ++w;
+      }
+    __syncthreads();
+    for (int j = tid; j < nr; j += kTieThreads)
+      D[j] = __longlong_as_double(
+          (long long)(((unsigned long long)(unsigned)Lb[j] << 32) | (unsigned)Rb[j]));
+    __syncthreads();
+    ref_sort_prefix(D, P, Lb, Rb, nr, sink.k, s);
+    ref_finish(q, D, P, sink.k, t.lab, sink.idx_off, class_cnt, cnt, sink);
+  }
+}
+
 // ---- the same for the train-sharded mode (north_star mode b).  The
 // reference's std::sort runs over all N_train records of the WHOLE train set
 // in global row order (cpp:360-366), so its order among equal distances
@@ -1888,6 +1945,19 @@ void launch_tie_order(int metric, const TrainDev& t, const double* Q64, const in
   else
     hipLaunchKernelGGL(tie_order_kernel<1>, dim3(nwg), dim3(kTieThreads), 0, s, t, Q64, tie_q,
                        tie_cnt, class_cnt, scratch, per_wg, sink, totals, excl);
+}
+
+void launch_tie_order_group(int metric, const TrainDev& t, const double* Q64, const int* tie_q,
+                            const int* tie_cnt, int class_cnt, unsigned char* scratch,
+                            int64_t per_wg, int nwg, const Sink& sink, unsigned long long* totals,
+                            hipStream_t s, const int32_t* qgroup, const int32_t* groups) {
+  if (nwg <= 0) return;
+  if (metric == 0)
+    hipLaunchKernelGGL(tie_order_group_kernel<0>, dim3(nwg), dim3(kTieThreads), 0, s, t, Q64,
+                       tie_q, tie_cnt, class_cnt, scratch, per_wg, sink, totals, qgroup, groups);
+  else
+    hipLaunchKernelGGL(tie_order_group_kernel<1>, dim3(nwg), dim3(kTieThreads), 0, s, t, Q64,
+                       tie_q, tie_cnt, class_cnt, scratch, per_wg, sink, totals, qgroup, groups);
 }
 
 // ------------------------------------------------ large k (k > kMaxK)

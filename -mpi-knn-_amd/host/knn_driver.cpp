@@ -27,6 +27,12 @@
 // replaced by a leave-one-out sweep of the train set (knn_group_loo_sweep:
 // every train row classified against all the others), prints "K = <k> loo
 // accuracy = <acc>" per K, selects K the same way and runs the test pass.
+// --groups FILE (needs --loo --K_list): FILE holds one integer group id >= 0
+// per train row (read like the other CSV files, one value per row); the sweep
+// becomes leave-one-GROUP-out (knn_group_lgo_sweep: every train row judged
+// against the rows of all the other groups -- samples of one subject, copies
+// of one image), prints "K = <k> lgo accuracy = <acc>" per K and selects K the
+// same way.  Without the flag stdout is unchanged.
 // --confusion (with the default validation pass, --K_list or --loo): after that
 // pass's lines prints "confusion K = <k>" for the selected K, then class_cnt
 // lines of class_cnt space-separated counts (row = true class, column =
@@ -81,6 +87,7 @@ struct Config {
   bool timings = false;
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
+  std::string groups_file;      // --groups: with --loo, leave out the row's whole group
   bool confusion = false;       // --confusion: print the selected K's confusion matrix
   int vote = KNN_VOTE_UNIFORM;  // --weights uniform|distance
   bool csv_gpu = false;         // --csv gpu: the files are parsed on device 0
@@ -96,11 +103,14 @@ void usage() {
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
           "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--confusion]\n"
+          "  [--groups F]\n"
           "  [--tune KEY=VALUE]... [--weights uniform|distance] [--csv host|gpu]\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
           "  --loo needs --K_list: scores every K by leave-one-out on the train set instead\n"
           "  (no validation file is read)\n"
+          "  --groups F needs --loo --K_list: F holds one integer group id per train row;\n"
+          "  every row is judged without the rows of its own group (leave-one-group-out)\n"
           "  --confusion prints the confusion matrix of the validation (or --loo) pass at the\n"
           "  selected K: class_cnt rows (true class) of class_cnt counts (predicted class)\n"
           "  --weights distance: every pass votes with weight 1 / distance (exact matches\n"
@@ -158,6 +168,7 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "validation_file") c.validation_file = v;
     else if (a == "test_file") c.test_file = v;
     else if (a == "output") c.output = v;
+    else if (a == "groups") c.groups_file = v;
     else if (a == "gpus") c.gpus = atoi(v.c_str());
     else if (a == "mode") c.mode = (v == "train" || v == "1") ? 1 : 0;
     else if (a == "strict") c.strict = parse_bool(v);
@@ -259,6 +270,8 @@ int main(int argc, char** argv) {
   if (c.dim <= 0 || c.K < 0 || c.N_train <= 0 || c.N_test < 0 || c.N_val < 0 || c.class_cnt <= 0)
     die("bad configuration");
   if (c.loo && c.K_list.empty()) die("--loo needs --K_list (the K to judge by leave-one-out)");
+  if (!c.groups_file.empty() && (!c.loo || c.K_list.empty()))
+    die("--groups needs --loo --K_list (the groups are left out of the leave-one-out sweep)");
   if (c.loo) c.Validation = false;  // the train set is its own validation set: no file is read
   if (c.strict && (c.N_train % c.gpus || c.N_test % c.gpus || (c.Validation && c.N_val % c.gpus)))
     die("N_train/N_test/N_val not divisible by the number of GPUs (--strict, cpp:127-129)");
@@ -301,6 +314,20 @@ int main(int argc, char** argv) {
   load(c.train_file, c.dim, true, c.N_train, Xtr, &Ltr, c.threads, gc);
   load(c.test_file, c.dim, false, c.N_test, Xte, nullptr, c.threads, gc);
   if (c.Validation) load(c.validation_file, c.dim, true, c.N_val, Xva, &Lva, c.threads, gc);
+  std::vector<int32_t> groups;  // --groups: one id per train row
+  int32_t n_groups = 0;
+  if (!c.groups_file.empty()) {
+    std::vector<double> Gv;
+    load(c.groups_file, 1, false, c.N_train, Gv, nullptr, c.threads, gc);
+    groups.resize((size_t)c.N_train);
+    for (long long i = 0; i < c.N_train; i++) {
+      const double v = Gv[(size_t)i];
+      if (!(v >= 0.0 && v < (double)INT32_MAX) || v != (double)(int32_t)v)
+        die(c.groups_file + ": row " + std::to_string(i) + " is not an integer group id >= 0");
+      groups[(size_t)i] = (int32_t)v;
+      n_groups = std::max(n_groups, groups[(size_t)i] + 1);
+    }
+  }
   phase("csv");
   if (gc && c.timings) {
     static const char* const names[5] = {"read", "h2d", "parse", "d2h", "slow"};
@@ -330,17 +357,26 @@ int main(int argc, char** argv) {
     std::vector<int32_t> pred((size_t)nk * c.N_train);
     std::vector<int64_t> correct(nk, 0);
     std::vector<int64_t> conf(c.confusion ? nk * cc : 0, 0), unl(c.confusion ? nk : 0, 0);
-    if (c.confusion
-            ? knn_group_loo_sweep_eval(g, c.K_list.data(), nk, metric, pred.data(), correct.data(),
-                                       conf.data(), unl.data())
-            : knn_group_loo_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data()))
+    const bool lgo = !groups.empty();
+    if (lgo) {  // every row without the rows of its own group
+      if (knn_group_set_groups(g, groups.data(), n_groups)) die(knn_last_error());
+      if (knn_group_lgo_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data(),
+                              c.confusion ? conf.data() : nullptr,
+                              c.confusion ? unl.data() : nullptr))
+        die(knn_last_error());
+    } else if (c.confusion
+                   ? knn_group_loo_sweep_eval(g, c.K_list.data(), nk, metric, pred.data(),
+                                              correct.data(), conf.data(), unl.data())
+                   : knn_group_loo_sweep(g, c.K_list.data(), nk, metric, pred.data(),
+                                         correct.data()))
       die(knn_last_error());
     double best = -1.0;
     int32_t sel = 0;
     for (int32_t i = 0; i < nk; i++) {
       double acc = (double)correct[i];  // acc_calc, cpp:69-84
       acc /= c.N_train;
-      std::cout << "K = " << c.K_list[i] << " loo accuracy = " << acc << std::endl;
+      std::cout << "K = " << c.K_list[i] << (lgo ? " lgo" : " loo") << " accuracy = " << acc
+                << std::endl;
       if (acc > best) {  // first to strictly exceed, like cpp:332-335
         best = acc;
         c.K = c.K_list[i];

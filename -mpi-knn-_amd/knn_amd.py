@@ -47,6 +47,9 @@ EXPORTED = (
     "knn_group_classify_sweep_eval", "knn_group_loo_sweep_eval",
     "knn_set_vote", "knn_get_vote", "knn_group_set_vote", "knn_vote_sweep_weighted_device",
     "knn_vote_weights_device",
+    "knn_set_groups", "knn_set_groups_device", "knn_get_group_max",
+    "knn_classify_sweep_gexcl_device", "knn_lgo_sweep_device", "knn_lgo_sweep",
+    "knn_group_set_groups", "knn_group_lgo_sweep",
     "knn_csv_parse_device", "knn_csv_read", "knn_csv_read_device", "knn_csv_last_slow",
     "knn_csv_last_phases",
 )
@@ -177,6 +180,15 @@ def lib():
         "knn_vote_sweep_weighted_device": ([P, P, P, i64, i32, P, i64, P, i32, P, P, P, P],
                                            ctypes.c_int),
         "knn_vote_weights_device": ([P, P, P, i64, i32, P, i64, i32, i32, P, P], ctypes.c_int),
+        "knn_set_groups": ([P, P, i32], ctypes.c_int),
+        "knn_set_groups_device": ([P, P, i32], ctypes.c_int),
+        "knn_get_group_max": ([P], i32),
+        "knn_classify_sweep_gexcl_device": ([P, P, i64, P, P, i32, i32, P, P, P, P, P, P, P],
+                                            ctypes.c_int),
+        "knn_lgo_sweep_device": ([P, i64, i64, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
+        "knn_lgo_sweep": ([P, P, i32, i32, P, P, P, P, P, P, P], ctypes.c_int),
+        "knn_group_set_groups": ([P, P, i32], ctypes.c_int),
+        "knn_group_lgo_sweep": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
         "knn_csv_parse_device": ([P, P, i64, i32, i32, i64, P, P, P, P, i64, P, P], ctypes.c_int),
         "knn_csv_read": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
         "knn_csv_read_device": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
@@ -327,7 +339,7 @@ class Classifier:
         return dC.cpu().numpy()
 
     def classify_sweep(self, Q, ks, metric=L2, truth=None, return_neighbors=False, exclude=None,
-                       confusion=False):
+                       confusion=False, exclude_group=None):
         """Labels for every K of `ks` (any order, duplicates allowed) from one
         search at max(ks): labels int32[nk, m], row i for ks[i].  With `truth`
         (int32[m]) also correct int64[nk] = (labels[i] == truth).sum().  With
@@ -336,6 +348,10 @@ class Classifier:
         answered as if train row exclude[i] were not in the train set
         (knn_classify_sweep_excl_device; staged through torch device tensors);
         then every K <= n_train - 1.
+        `exclude_group` (int32[m], group ids as in set_groups; -1 or any id no
+        row carries = none; not together with `exclude`): query i is answered
+        as if no train row of group exclude_group[i] were in the train set
+        (knn_classify_sweep_gexcl_device); then every K <= n_train - group_max().
         confusion=True (needs `truth`; not with return_neighbors) appends conf
         int64[nk, C, C] (row = true class, column = predicted) and unl
         int64[nk] (queries whose label or truth is outside [0, C)):
@@ -349,6 +365,15 @@ class Classifier:
             truth = np.ascontiguousarray(truth, dtype=np.int32)
             if truth.shape != (m,):
                 raise ValueError("truth must have one label per query")
+        if exclude_group is not None:
+            if exclude is not None:
+                raise ValueError("exclude and exclude_group are mutually exclusive")
+            qg = np.ascontiguousarray(exclude_group, dtype=np.int32)
+            if qg.shape != (m,):
+                raise ValueError("exclude_group must have one group id (or -1) per query")
+            if confusion and (truth is None or return_neighbors):
+                raise ValueError("confusion needs truth and excludes return_neighbors")
+            return self._sweep_gexcl(Q, qg, ks, kmax, metric, truth, return_neighbors, confusion)
         if exclude is not None:
             exclude = np.ascontiguousarray(exclude, dtype=np.int64)
             if exclude.shape != (m,):
@@ -403,6 +428,36 @@ class Classifier:
         out = (dL.cpu().numpy(),)
         if truth is not None:
             out += (dC.cpu().numpy(),)
+        if return_neighbors:
+            out += (dI.cpu().numpy()[:, :kmax], dD.cpu().numpy()[:, :kmax], dF.cpu().numpy())
+        return out[0] if len(out) == 1 else out
+
+    def _sweep_gexcl(self, Q, qgroup, ks, kmax, metric, truth, return_neighbors, confusion):
+        import torch
+        dev = torch.device("cuda", self.device)
+        m, nk, C = Q.shape[0], ks.shape[0], self.class_cnt
+        dQ = torch.from_numpy(Q).to(dev)
+        dG = torch.from_numpy(qgroup).to(dev)
+        dT = torch.from_numpy(truth).to(dev) if truth is not None else None
+        dL = torch.empty((nk, m), dtype=torch.int32, device=dev)
+        dC = torch.zeros(nk, dtype=torch.int64, device=dev) if truth is not None else None
+        dF = torch.empty(m, dtype=torch.int32, device=dev)
+        dI = torch.empty((m, max(kmax, 1)), dtype=torch.int64, device=dev) if return_neighbors else None
+        dD = torch.empty((m, max(kmax, 1)), dtype=torch.float64, device=dev) if return_neighbors else None
+        dM = torch.zeros((nk, C, C), dtype=torch.int64, device=dev) if confusion else None
+        dU = torch.zeros(nk, dtype=torch.int64, device=dev) if confusion else None
+        torch.cuda.synchronize(dev)  # the context's stream is not torch's
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.classify_sweep_gexcl_device(p(dQ), m, p(dG), ks, metric, p(dL), p(dT), p(dC), p(dI),
+                                         p(dD), p(dF))
+        if confusion:  # on the context's stream, after the sweep
+            self.confusion_device(p(dL), nk, m, p(dT), C, p(dM), p(dU))
+        self.sync()
+        out = (dL.cpu().numpy(),)
+        if truth is not None:
+            out += (dC.cpu().numpy(),)
+        if confusion:
+            out += (dM.cpu().numpy(), dU.cpu().numpy())
         if return_neighbors:
             out += (dI.cpu().numpy()[:, :kmax], dD.cpu().numpy()[:, :kmax], dF.cpu().numpy())
         return out[0] if len(out) == 1 else out
@@ -530,6 +585,80 @@ class Classifier:
         if return_neighbors:
             return labels, correct, idx[:, :kmax], dist[:, :kmax], flags
         return labels, correct
+
+    def set_groups(self, groups, n_groups=None):
+        """Attaches a group id per train row (int32[n_train], 0 <= id <
+        n_groups; n_groups defaults to max id + 1) for exclude_group= and
+        lgo_sweep (knn_set_groups); None clears them, and so does set_train.
+        An id out of range raises KnnError naming the row."""
+        if groups is None:
+            _check(lib().knn_set_groups(self._h, None, 0))
+            return
+        groups = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if self.n_train and groups.shape[0] != self.n_train:
+            raise ValueError("groups must have one id per train row")
+        if n_groups is None:
+            n_groups = int(groups.max()) + 1 if groups.size else 1
+        _check(lib().knn_set_groups(self._h, _ptr(groups), int(n_groups)))
+
+    def set_groups_device(self, d_groups, n_groups, keep=None):
+        """Device pointer variant (borrowed; `keep` holds the owning tensor)."""
+        _check(lib().knn_set_groups_device(self._h, d_groups, int(n_groups)))
+        self._keep_groups = keep
+
+    def group_max(self):
+        """Rows of the largest group; 0 when no groups are set."""
+        return int(lib().knn_get_group_max(self._h))
+
+    def lgo_sweep(self, ks, metric=L2, return_neighbors=False, confusion=False, labels=True):
+        """Leave-one-group-out K sweep over the whole train set (knn_lgo_sweep):
+        every train row classified against the train rows of all the OTHER
+        groups at every K of `ks` (each <= n_train - group_max()).  Returns as
+        loo_sweep: (labels int32[nk, n], correct int64[nk]), with
+        confusion=True also conf int64[nk, C, C] and unl int64[nk] (labels=False
+        drops the label array), with return_neighbors also (idx[n, kmax],
+        dist[n, kmax], flags[n]) at the end."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk, n = ks.shape[0], self.n_train
+        kmax = int(ks.max()) if nk else 0
+        if not labels and not confusion:
+            raise ValueError("labels=False needs confusion=True")
+        C = self.class_cnt
+        out_lab = np.empty((nk, n), np.int32) if labels else None
+        correct = np.zeros(nk, np.int64)
+        conf = np.zeros((nk, C, C), np.int64) if confusion else None
+        unl = np.zeros(nk, np.int64) if confusion else None
+        flags = np.empty(n, np.int32) if return_neighbors else None
+        idx = np.empty((n, max(kmax, 1)), np.int64) if return_neighbors else None
+        dist = np.empty((n, max(kmax, 1)), np.float64) if return_neighbors else None
+        _check(lib().knn_lgo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(out_lab),
+                                   _ptr(correct), _ptr(conf), _ptr(unl), _ptr(idx), _ptr(dist),
+                                   _ptr(flags)))
+        out = (out_lab, correct) if labels else (correct,)
+        if confusion:
+            out += (conf, unl)
+        if return_neighbors:
+            out += (idx[:, :kmax], dist[:, :kmax], flags)
+        return out
+
+    def lgo_sweep_device(self, row0, rows, ks, metric, d_labels, d_correct=None, d_idx=None,
+                         d_dist=None, d_flags=None, stream=None):
+        """Leave-group-out sweep of train rows [row0, row0 + rows) into device
+        buffers (enqueue only): d_labels [nk][rows], d_correct [nk]."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_lgo_sweep_device(self._h, int(row0), int(rows), _ptr(ks), ks.shape[0],
+                                          int(metric), d_labels, d_correct, d_idx, d_dist, d_flags,
+                                          stream))
+
+    def classify_sweep_gexcl_device(self, dQ_ptr, m, d_qgroup, ks, metric, d_labels, d_truth=None,
+                                    d_correct=None, d_idx=None, d_dist=None, d_flags=None,
+                                    stream=None):
+        """Device-pointer sweep under group exclusion (enqueue only): d_qgroup
+        device int32[m], each query's group (-1 = none); None: the plain sweep."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_classify_sweep_gexcl_device(self._h, dQ_ptr, m, d_qgroup, _ptr(ks),
+                                                     ks.shape[0], int(metric), d_labels, d_truth,
+                                                     d_correct, d_idx, d_dist, d_flags, stream))
 
     def loo_sweep_device(self, row0, rows, ks, metric, d_labels, d_correct=None, d_idx=None,
                          d_dist=None, d_flags=None, stream=None):
@@ -852,6 +981,35 @@ class Group:
         _check(lib().knn_group_loo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(labels),
                                          _ptr(correct)))
         return labels, correct
+
+    def set_groups(self, groups, n_groups=None):
+        """Classifier.set_groups on every rank (mode 0; mode 1 raises KnnError)."""
+        if groups is None:
+            _check(lib().knn_group_set_groups(self._h, None, 0))
+            return
+        groups = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if self.n_train and groups.shape[0] != self.n_train:
+            raise ValueError("groups must have one id per train row")
+        if n_groups is None:
+            n_groups = int(groups.max()) + 1 if groups.size else 1
+        _check(lib().knn_group_set_groups(self._h, _ptr(groups), int(n_groups)))
+
+    def lgo_sweep(self, ks, metric=L2, confusion=False, labels=True):
+        """Classifier.lgo_sweep over the group (mode 0; mode 1 raises KnnError):
+        the results of loo_sweep, under group exclusion."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk = ks.shape[0]
+        if not labels and not confusion:
+            raise ValueError("labels=False needs confusion=True")
+        C = self.class_cnt
+        out_lab = np.empty((nk, self.n_train), np.int32) if labels else None
+        correct = np.zeros(nk, np.int64)
+        conf = np.zeros((nk, C, C), np.int64) if confusion else None
+        unl = np.zeros(nk, np.int64) if confusion else None
+        _check(lib().knn_group_lgo_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(out_lab),
+                                         _ptr(correct), _ptr(conf), _ptr(unl)))
+        out = (out_lab, correct) if labels else (correct,)
+        return out + (conf, unl) if confusion else out
 
     def last_compute_seconds(self):
         return float(lib().knn_group_last_compute_seconds(self._h))

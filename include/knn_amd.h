@@ -305,6 +305,66 @@ int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metr
                        int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
                        int64_t* out_unl);
 
+/* ---- K sweep under group exclusion / leave-one-group-out.  Leave-one-out
+ * overstates accuracy whenever train rows are not independent (several samples
+ * per writer, patient or subject, augmented copies of one image, exact
+ * duplicates): the held-out row's siblings stay in the train set and vote for
+ * it.  A train set may carry a group id per row, groups[n] (int32, 0 <= id <
+ * n_groups; singletons get ids of their own), and a query a group gq.  One
+ * rule fixes every output: the result is what knn_classify_sweep returns on a
+ * context whose train set is the current one WITH EVERY ROW r, groups[r] ==
+ * gq, REMOVED (labels lose the same entries), reported indices mapped back to
+ * the full train set.  That covers the label at every K, the neighbour
+ * indices, their order and the distances, the flag bits
+ * KNN_FLAG_TIE_BOUNDARY | TIE_VOTE | TIE_ORDER | TIE_REF and the rows "ties" =
+ * 0 / 1 / 2 re-order: the order among equal distances is the reference's
+ * std::sort over the n - c remaining records in row order (cpp:323), another
+ * introsort run than the ones over n or n - 1.  KNN_FLAG_EXACT_RESCAN may
+ * differ.  gq = -1, or any gq outside [0, n_groups), excludes nothing: that
+ * query equals the plain sweep's.  KNN_VOTE_DISTANCE applies as in every sweep.
+ * One search at max(ks) + gmax serves a call (gmax: the largest group's
+ * size): large groups are served correctly, but through that wide search --
+ * masking the group inside the candidate pass (k-fold with folds of thousands
+ * of rows) is not done here.
+ *
+ * knn_set_groups / knn_set_groups_device attach the ids to the current train
+ * set (local rows, [n_train]); the host variant copies them, the device
+ * variant borrows the pointer as knn_set_train_device borrows its labels.
+ * KNN_ERR_STATE before a train set exists; KNN_ERR_ARG for an id outside [0,
+ * n_groups), naming the first such row (checked on the device, with the
+ * histogram of group sizes that gives gmax; the call waits for both, as
+ * set_train does for its checks) -- no groups are set then.  groups NULL
+ * clears them, and so does every knn_set_train*.  knn_get_group_max: gmax, 0
+ * when no groups are set. */
+int knn_set_groups(knn_ctx* ctx, const int32_t* groups, int32_t n_groups);
+int knn_set_groups_device(knn_ctx* ctx, const int32_t* d_groups, int32_t n_groups);
+int32_t knn_get_group_max(knn_ctx* ctx);
+/* knn_classify_sweep_excl_device with d_qgroup [m] (device, int32: each
+ * query's group) in place of d_excl.  d_qgroup NULL = the plain sweep.  With
+ * d_qgroup non-NULL: KNN_ERR_STATE when no groups are set, and ks[i] <=
+ * n_train - gmax (KNN_ERR_ARG names the offending entry).  Enqueue only, on
+ * the stream on_stream (NULL: the context's own), like its siblings. */
+int knn_classify_sweep_gexcl_device(knn_ctx* ctx, const double* dQ, int64_t m,
+                                    const int32_t* d_qgroup, const int32_t* ks, int32_t nk,
+                                    int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                                    int64_t* d_correct, int64_t* d_idx, double* d_dist,
+                                    int32_t* d_flags, void* on_stream);
+/* Leave-group-out over train rows [row0, row0 + rows) (as
+ * knn_loo_sweep_device): query i excludes the group of row row0 + i, and so
+ * itself; its truth is its own label.  0 <= ks[i] <= n_train - gmax.
+ * Enqueue only. */
+int knn_lgo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
+                         int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                         double* d_dist, int32_t* d_flags, void* on_stream);
+/* Host twin over all n_train rows in the 16384-row batches of knn_loo_sweep
+ * (waits for the result).  out_conf [nk*C*C] and out_unl [nk] (nullable) are
+ * summed over the batches on the device (knn_confusion_device); out_labels
+ * [nk][n] is nullable when out_conf is given; out_correct [nk], out_idx /
+ * out_dist [n*kmax], out_flags [n] nullable. */
+int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
+                  int64_t* out_correct, int64_t* out_conf, int64_t* out_unl, int64_t* out_idx,
+                  double* out_dist, int32_t* out_flags);
+
 /* ---- distance-weighted voting: the second hyperparameter of a KNN classifier.
  * The vote mode is state of the context, like the precision:
  *   KNN_VOTE_UNIFORM (default): the reference's first-to-strictly-exceed vote
@@ -718,6 +778,18 @@ int knn_group_classify_sweep_eval(knn_group* g, const double* Q, int64_t m, cons
 int knn_group_loo_sweep_eval(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
                              int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
                              int64_t* out_unl);
+/* Leave-group-out over the group (see knn_set_groups and knn_lgo_sweep), mode
+ * 0 only.  knn_group_set_groups: groups [n] (host; NULL clears) go to every
+ * rank's copy of the train set; knn_group_set_train clears them.
+ * knn_group_lgo_sweep: rank r takes rows [n r / G, n (r + 1) / G) in batches
+ * of at most 16384 rows, as knn_group_loo_sweep; out_labels [nk][n] (nullable
+ * when out_conf is given), out_correct, out_conf [nk*C*C], out_unl [nk]
+ * nullable, summed over the ranks on the host.  mode 1 (train-sharded): not
+ * served by either call, KNN_ERR_ARG with a message saying so. */
+int knn_group_set_groups(knn_group* g, const int32_t* groups, int32_t n_groups);
+int knn_group_lgo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                        int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                        int64_t* out_unl);
 /* Seconds of the last group classify spent between the first enqueue and
  * the last device completion (device-resident inputs, excludes H2D/D2H). */
 double knn_group_last_compute_seconds(knn_group* g);
