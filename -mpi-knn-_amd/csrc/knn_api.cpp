@@ -335,6 +335,7 @@ static int build_train(knn_ctx* ctx, const double* dX, const int32_t* dlab, int6
   ctx->DPi = 0;
   ctx->DPiw = 0;
   ctx->DPu = 0;
+  ctx->DPuw = 0;
   ctx->smp_kind = 0;  // the seeding sample is rebuilt for the new train set
   ctx->i8_off = false;
   ctx->fp16_off = false;
@@ -472,6 +473,32 @@ static int ensure_u16(knn_ctx* ctx, hipStream_t s) {
   memcpy(&ctx->u16_dx, &ctx->h_stats[3], 8);
   ctx->u16_e = e;
   ctx->DPu = DPu;
+  return KNN_OK;
+}
+
+// The image of kernel metric 8 at 256 < d <= 1024 (knn_cand_fix16_wide.hip):
+// the same codes at the same scale as 32-row tiles of dim slabs, in its own
+// buffer, built on the first such call (train order: no region order and no
+// norm blocks above 256 dims); u16_dx is measured by the same row pass.
+static int ensure_u16_wide(knn_ctx* ctx, hipStream_t s) {
+  const TrainDev& t = ctx->train;
+  const int DPw = pad_dim_u16l1w(t.d);
+  if (DPw <= 0)
+    return knn_fail(KNN_ERR_ARG, "wide 16-bit fixed-point L1 pass supports 256 < d <= 1024");
+  if (ctx->DPuw == DPw) return KNN_OK;
+  int rc;
+  if ((rc = ctx->XUW.ensure((size_t)t.n_pad * DPw * sizeof(unsigned short)))) return rc;
+  const int e = t.jx + 5;
+  unsigned long long* st_d = (unsigned long long*)ctx->stats.p + 3;
+  HIP_TRY(hipMemsetAsync(st_d, 0, 8, s));
+  launch_prep_u16_train_wide(t.X64, t.mu, t.n, t.d, DPw, t.n_pad, e, (unsigned short*)ctx->XUW.p,
+                             st_d, s, t.perm);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ctx->h_stats + 3, st_d, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(&ctx->u16_dx, &ctx->h_stats[3], 8);
+  ctx->u16_e = e;
+  ctx->DPuw = DPw;
   return KNN_OK;
 }
 
@@ -684,6 +711,7 @@ static int ensure_image(knn_ctx* ctx, const SearchPlan& p, hipStream_t s) {
     case IMG_I8: return ensure_i8(ctx, p.kmetric, s);
     case IMG_I8W: return ensure_i8_wide(ctx, s);
     case IMG_U16: return ensure_u16(ctx, s);
+    case IMG_U16W: return ensure_u16_wide(ctx, s);
     case IMG_FP16: return ensure_fp16(ctx, s);
     case IMG_FP16_S3: return ensure_fp16_s3(ctx, s);
     case IMG_BF16X3: return ensure_bf16x3(ctx, s);
@@ -707,7 +735,7 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   const int64_t m_pad = p.m_pad;
   const float* const images[] = {t.X32, (const float*)ctx->XB.p, (const float*)ctx->XH.p, nullptr,
                                  (const float*)ctx->XI.p, (const float*)ctx->XIW.p,
-                                 (const float*)ctx->XU.p};
+                                 (const float*)ctx->XU.p, (const float*)ctx->XUW.p};
   // the int8 passes (kernel metrics 5-7) share their query builder, centre
   // and scale; metric 8 takes the fp32 paths' query check and threshold fill
   const bool i8p = kmetric >= 5 && kmetric <= 7;
@@ -781,7 +809,10 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   if (!i8p)
     launch_query_check(dQ, t.mu, m, t.d, m_pad, qscale, t.jx,
                        kmetric == 4 ? 65000.0 : std::ldexp(1.0, 100), qvalid, s);
-  if (kmetric == 8)
+  if (p.image == IMG_U16W)
+    launch_prep_u16_queries_wide(dQ, t.mu, m, t.d, DP, m_pad, ctx->u16_e,
+                                 (unsigned short*)ctx->Q32.p, qvalid, s);
+  else if (kmetric == 8)
     launch_prep_u16_queries(dQ, t.mu, m, t.d, DP, m_pad, ctx->u16_e, (unsigned short*)ctx->Q32.p,
                             qvalid, s);
   else if (i8p) {  // codes of the train set's grid; a query off it: valid 0 (rescan)
@@ -906,11 +937,12 @@ int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
   if (kmetric == 8) {
     // 16-bit fixed-point L1 proxies are in units of 2^-e; their error is the
     // two vectors' measured coding errors (the merge rebuilds the query's
-    // codes) plus err_factor(8)'s fp64 rounding terms
+    // codes) plus err_factor(8)'s fp64 rounding terms; above 256 dims the
+    // sums' conversion to float adds fix16_wide_round code units (0 below)
     TrainDev tu = t;
     tu.jx = ctx->u16_e;
     ProxyScale ps{qvalid, 0.0, 0.0, false, nullptr, qpos};
-    ps.u16dx = ctx->u16_dx;
+    ps.u16dx = ctx->u16_dx + fix16_wide_round(DP);
     launch_merge_rerank(metric, (const float*)ctx->cand_v.p, (const int*)ctx->cand_i.p, NL, R, tu,
                         dQ, m, W, C, err_factor(8, DP), ps, cl.gthr, sink, (int*)ctx->rescan_q.p,
                         (double*)ctx->rescan_tau.p, (int*)ctx->rescan_cnt.p, sm, rp, s);

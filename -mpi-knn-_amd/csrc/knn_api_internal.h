@@ -92,6 +92,10 @@ struct knn_ctx {
   DevBuf XU;
   int DPu = 0, u16_e = 0;
   double u16_dx = 0.0;
+  // its wide form's own image (256 < d <= 1024): 32-row tiles of dim slabs,
+  // DPuw codes per row, n_pad rows (0 = not built); u16_e and u16_dx as above
+  DevBuf XUW;
+  int DPuw = 0;
   DevBuf smp_x64, smp_xl2, smp_img, smp_scr, smp_v, smp_i;
   // region order: centroids [P][d], chain ranks, region starts, image
   // position <-> train row maps; k-means / sort scratch; per-call query order
@@ -132,7 +136,7 @@ struct knn_ctx {
   int64_t csv_last_slow = -1;                  // slow tokens of the last file call
   double csv_phase_s[5] = {0, 0, 0, 0, 0};     // its read / h2d / parse / d2h / slow seconds
   std::vector<DevBuf*> all_bufs() {
-    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &XU, &i8_cent, &i8_gs,
+    return {&X64_own, &lab_own, &X32,   &xl2,   &xl1,    &stats,  &XB,       &XS, &XI, &XIW, &XU, &XUW, &i8_cent, &i8_gs,
             &XH,      &XT16,    &XS16,  &mu,      &mu_part, &Q64, &Q32,    &qvalid, &cand_v,   &cand_i,
             &gthr,    &rescan_q, &rescan_tau, &rescan_cnt, &fr_cnt, &fr_buf, &fr_q, &fr_thr,
             &slow_q,  &totals,  &lk, &mrg, &tie_q, &tie_ws, &o_lab, &o_idx, &o_dist, &o_flags, &nrm_part, &nrm_mm, &nrm_X,

@@ -612,7 +612,7 @@ static void launch_str(const CandLaunch& c, hipStream_t s) {
 
 int cand_blocks_per_cu(int metric, int DP, int R, int nw) {
   if (metric == 7) return DP > 256 ? sad_wide_blocks_per_cu(R, nw) : sad_blocks_per_cu(DP, R, nw);
-  if (metric == 8) return fix16_blocks_per_cu(DP, R, nw);
+  if (metric == 8) return DP > 256 ? fix16_wide_blocks_per_cu(R, nw) : fix16_blocks_per_cu(DP, R, nw);
   if (metric == 2 && bf16x3_streamed(DP)) return s3_blocks_per_cu(R);
   if (metric == 4 && DP > 256) return s3h_blocks_per_cu(R);
 #define KNN_CASE(v) if (DP == v) return blocks_res_##v(R, metric, nw);
@@ -640,7 +640,7 @@ int cand_queries_per_wave(int metric, int DP) {
 
 int cand_tile_rows(int metric, int DP) {
   if (metric == 7) return DP > 256 ? sad_wide_tile_rows() : sad_tile_rows(DP);
-  if (metric == 8) return fix16_tile_rows(DP);
+  if (metric == 8) return DP > 256 ? fix16_wide_tile_rows() : fix16_tile_rows(DP);
   if ((metric == 2 && bf16x3_streamed(DP)) || (metric == 4 && DP > 256)) return kS3R;
 #define KNN_CASE(v) if (DP == v) return trows_res_##v(metric);
   KNN_DP_LIST(KNN_CASE)
@@ -650,7 +650,7 @@ int cand_tile_rows(int metric, int DP) {
 
 bool launch_cand(const CandLaunch& c, hipStream_t s) {
   if (c.metric == 7) return c.DP > 256 ? launch_cand_sad_wide(c, s) : launch_cand_sad(c, s);
-  if (c.metric == 8) return launch_cand_fix16(c, s);
+  if (c.metric == 8) return c.DP > 256 ? launch_cand_fix16_wide(c, s) : launch_cand_fix16(c, s);
 #define KNN_CASE(v) \
   if (c.DP == v) return launch_res_##v(c, s);
   KNN_DP_LIST(KNN_CASE)

@@ -33,6 +33,17 @@ int pad_dim_i8l1w(int d);
 // multiple of 32 up to 256 (65535 * 256 < 2^24: the sums stay exact floats),
 // -1 beyond
 int pad_dim_u16l1(int d);
+// padded dim of the wide 16-bit fixed-point L1 image (knn_cand_fix16_wide.hip):
+// d in (256, 1024] rounded up to 16, -1 outside.  65535 * 1024 < 2^26: the
+// sums are exact integers and floats within fix16_wide_round code units
+int pad_dim_u16l1w(int d);
+// |fl32(P) - P| at most, for a sum P of DP code differences (code units): 0
+// below 2^24 (DP <= 256), half an ulp of [2^24, 2^25) up to DP = 512, of
+// [2^25, 2^26) up to DP = 1024
+constexpr int fix16_wide_round(int DP) { return DP <= 256 ? 0 : DP <= 512 ? 1 : 2; }
+// that image's dim slabs: a row of cpr 16-byte chunks (8 codes each) is one
+// slab up to 64 chunks (512 dims), two halves above; chunks of the first slab
+constexpr int fix16_wide_slab0(int cpr) { return cpr > 64 ? (cpr + 1) / 2 : cpr; }
 
 #define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
 

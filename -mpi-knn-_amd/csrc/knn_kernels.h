@@ -186,7 +186,15 @@ int sad_wide_tile_rows();
 bool launch_cand_fix16(const CandLaunch& c, hipStream_t s);
 int fix16_blocks_per_cu(int DP, int R, int nw);
 int fix16_tile_rows(int DP);
-// Its operands (knn_prep.hip): rows of DP unsigned 16-bit codes
+// kernel metric 8 at 256 < DP <= 1024 (knn_cand_fix16_wide.hip): X32 = the
+// tiles of dim slabs of launch_prep_u16_train_wide, Q32 = the step-major query
+// codes of launch_prep_u16_queries_wide.  Its proxies are floats within
+// fix16_wide_round(DP) code units of the integer sums (knn_dims.h).
+bool fix16_wide_dp(int DP);
+bool launch_cand_fix16_wide(const CandLaunch& c, hipStream_t s);
+int fix16_wide_blocks_per_cu(int R, int nw);
+int fix16_wide_tile_rows();
+// The narrow kernel's operands (knn_prep.hip): rows of DP unsigned 16-bit codes
 // clamp(rint(2^e (x - mu)), -32768, 32767) + 32768, zero codes in the pad dims
 // and on pad rows.  Train: n_pad rows, image row p <- train row perm[p];
 // dmax receives the largest row sum of |code - 32768 - 2^e (x - mu)| (code
@@ -198,6 +206,18 @@ void launch_prep_u16_train(const double* X64, const double* mu, int64_t n, int d
 void launch_prep_u16_queries(const double* Q64, const double* mu, int64_t m, int d, int DP,
                              int64_t m_pad, int e, unsigned short* out, const float* valid,
                              hipStream_t s);
+// The wide kernel's operands: the same codes, DP a multiple of 16 in (256,
+// 1024], a row of DP / 8 16-byte chunks cut into fix16_wide_slab0's dim
+// slabs.  Train (train order, n_pad a multiple of 32): 32-row tiles, within a
+// tile slab after slab, each as 32 rows of the slab's chunks; dmax as above.
+// Queries (m_pad a multiple of 32): step-major, the 8 codes of step c of query
+// j of 32-query group g at uint4 index (g * DP / 8 + c) * 32 + j.
+void launch_prep_u16_train_wide(const double* X64, const double* mu, int64_t n, int d, int DP,
+                                int64_t n_pad, int e, unsigned short* out,
+                                unsigned long long* dmax, hipStream_t s, const int* perm = nullptr);
+void launch_prep_u16_queries_wide(const double* Q64, const double* mu, int64_t m, int d, int DP,
+                                  int64_t m_pad, int e, unsigned short* out, const float* valid,
+                                  hipStream_t s);
 // gthr: the candidate kernel's per-query global thresholds ([m_pad][kGthrSlots] keys)
 // or null when the kernel kept none
 // failed queries are appended to rescan_q with rescan_tau = the W-th exact

@@ -64,6 +64,14 @@ int pad_dim_i8l1w(int d) {
 // 256 < 2^24, exact as floats
 int pad_dim_u16l1(int d) { return pad_dim_i8w(d); }
 
+// ... and above 256 dims (knn_cand_fix16_wide.hip): one ds_read_b128 of a row
+// is 8 codes and the query's steps come in pairs, so any multiple of 16 up to
+// 1024 (65535 * 1024 < 2^26: exact in the integer accumulators, and within
+// fix16_wide_round code units as floats); d = 784 pads nothing
+int pad_dim_u16l1w(int d) {
+  return d > 256 && d <= 1024 ? (d + 15) / 16 * 16 : -1;
+}
+
 // fp16 S3 kernel above 256 dims: any multiple of 32
 int pad_dim_fp16_s3(int d) {
   const int DP = (d + 31) / 32 * 32;
@@ -231,6 +239,16 @@ static bool use_u16l1(const PlanIn& in) {
   return in.metric == KNN_METRIC_L1 && in.tune.u16l1 == 1 && pad_dim_u16l1(in.d) > 0;
 }
 
+// The same pass at 256 < d <= 1024 (its wide form, knn_cand_fix16_wide.hip:
+// query codes re-read per tile, sums rounded to float within a bounded term).
+// Tuning key "u16l1w": 0 off (the default), 1 on at every batch size.  Opt-in
+// only, and a key of its own: "u16l1" moves no call above 256 dims.  Where
+// "i8l1" = 2 puts an integer-coded train set on the exact byte-code pass
+// (metric 7 wide), that pass wins: plan_search asks use_i8l1_wide first.
+static bool use_u16l1_wide(const PlanIn& in) {
+  return in.metric == KNN_METRIC_L1 && in.tune.u16l1w == 1 && pad_dim_u16l1w(in.d) > 0;
+}
+
 static bool use_bf16x3(const PlanIn& in) {
   if (in.metric != KNN_METRIC_L2) return false;
   if (in.precision == KNN_PRECISION_FP32) return false;
@@ -247,7 +265,10 @@ static bool resident_variant(int DP, int R, int M, int NW) {
     return (pad_dim_i8w(DP) == DP || pad_dim_i8l1w(DP) == DP) && (R == 8 || R == 16) &&
            (NW == 4 || NW == 8);
   // metric 8 (knn_cand_fix16.hip): DP of pad_dim_u16l1, R in {8, 16}, 4 waves,
-  // or 8 up to DP = 128 (the resident query takes DP / 2 registers)
+  // or 8 up to DP = 128 (the resident query takes DP / 2 registers); its wide
+  // form (knn_cand_fix16_wide.hip) takes DP at run time, 4 or 8 waves
+  if (M == 8 && DP > 256)
+    return pad_dim_u16l1w(DP) == DP && (R == 8 || R == 16) && (NW == 4 || NW == 8);
   if (M == 8)
     return pad_dim_u16l1(DP) == DP && (R == 8 || R == 16) && (NW == 4 || (NW == 8 && DP <= 128));
   return (M != 2 || DP % 16 == 0) && (M != 1 || (NW == 4 && R != 4)) &&
@@ -400,6 +421,12 @@ SearchPlan plan_search(const PlanIn& in) {
     p.kmetric = 8;
     p.image = IMG_U16;
     p.DP = pad_dim_u16l1(in.d);
+  } else if (use_u16l1_wide(in)) {
+    // the same pass on tiles of dim slabs (train order: no region order and
+    // no norm blocks above 256 dims)
+    p.kmetric = 8;
+    p.image = IMG_U16W;
+    p.DP = pad_dim_u16l1w(in.d);
   } else if (use_i8(in)) {
     p.kmetric = i8_kernel_d(tune, in.d);
     p.image = IMG_I8;
@@ -433,17 +460,19 @@ SearchPlan plan_search(const PlanIn& in) {
   else if (kmetric == 6 && tune.nw == 16) p.nw = 16;
   // L1 on int8 codes: 4 or 8 (256 queries share each staged tile)
   else if (kmetric == 7) p.nw = tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4);
-  // L1 on 16-bit codes: 8 only up to DP = 128 (no 8-wave kernel above it)
+  // L1 on 16-bit codes: 8 only up to DP = 128 (no 8-wave resident kernel above
+  // it); the wide form re-reads its queries and has both, as metric 7's
   else if (kmetric == 8)
-    p.nw = DP > 128 ? 4 : (tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4));
+    p.nw = DP > 128 && DP <= 256 ? 4
+                                 : (tune.nw == 4 || tune.nw == 8 ? tune.nw : (m >= 4096 ? 8 : 4));
   else if (kmetric >= 3) p.nw = 8;  // (the 16x16 layouts: fp16, bf16x3, int8)
   else if (DP <= 256 && kmetric != 1) p.nw = tune.nw ? std::min(tune.nw, 8) : (m >= 4096 ? 8 : 4);
   else p.nw = 4;
   // queries per wave of the resident kernel (int8: 16 x the build's query
   // blocks); the int8 kernel with 64 queries per wave also runs 4 waves
-  // (metric 7 at DP > 256 is a resident-style kernel too: its own facts, not
-  // the stream kernel's 128 queries)
-  const bool res = !p.s3 && (DP <= 256 || kmetric == 7);
+  // (metrics 7 and 8 at DP > 256 are resident-style kernels too: their own
+  // facts, not the stream kernel's 128 queries)
+  const bool res = !p.s3 && (DP <= 256 || kmetric == 7 || kmetric == 8);
   p.qpw = res ? in.facts.cand_queries_per_wave(kmetric, DP) : 32;
   p.qpb = p.s3 ? kS3Rows : (res ? p.qpw * p.nw : kQPB);
   p.n_qt = (int)((m + p.qpb - 1) / p.qpb);
@@ -545,7 +574,10 @@ SearchPlan plan_search(const PlanIn& in) {
       snprintf(p.kernel, sizeof p.kernel, "cand_sad_kernel<%d,%d,%d>", DP, p.R, p.nw);
     p.ok = resident_variant(DP, p.R, kmetric, p.nw);
   } else if (kmetric == 8) {
-    snprintf(p.kernel, sizeof p.kernel, "cand_fix16_kernel<%d,%d,%d>", DP, p.R, p.nw);
+    if (DP > 256)
+      snprintf(p.kernel, sizeof p.kernel, "cand_fix16_wide_kernel<%d,%d>", p.R, p.nw);
+    else
+      snprintf(p.kernel, sizeof p.kernel, "cand_fix16_kernel<%d,%d,%d>", DP, p.R, p.nw);
     p.ok = resident_variant(DP, p.R, kmetric, p.nw);
   } else if (DP <= 256) {
     snprintf(p.kernel, sizeof p.kernel, "cand_kernel<%d,%d,%d,%d>", DP, p.R, kmetric, p.nw);
@@ -574,6 +606,8 @@ SearchPlan plan_search(const PlanIn& in) {
 //     mu||_1 + max||x - mu||_1 >= the distance: v - mu before the coding (u64
 //     = 2^-53 per element, on both sides) and the reference's own loop (a
 //     subtraction and DP - 1 additions: gamma_DP) -- (DP + 4) u64, doubled.
+//     (Above 256 dims the sums' conversion to float adds fix16_wide_round(DP)
+//     code units, which the host folds into ProxyScale::u16dx.)
 double err_factor(int kmetric, int DP) {
   if (kmetric == 7) return 0.0;  // integer sums of code differences: exact
   if (kmetric == 8) return 2.0 * (DP + 4) * std::ldexp(1.0, -53);
@@ -621,6 +655,7 @@ const TuneKey kTuneKeys[] = {
     {"i8w", &Tuning::i8w, -1, 1, nullptr, "i8w must be -1, 0 or 1"},
     {"i8l1", &Tuning::i8l1, -1, 2, nullptr, "i8l1 must be -1, 0, 1 or 2 (2: also at 256 < d <= 1024)"},
     {"u16l1", &Tuning::u16l1, 0, 1, nullptr, "u16l1 must be 0 or 1"},
+    {"u16l1w", &Tuning::u16l1w, 0, 1, nullptr, "u16l1w must be 0 or 1 (1: at 256 < d <= 1024)"},
     {"s3gq", &Tuning::s3gq, 0, 0, kSetS3gq, "s3gq must be 0 (auto) or 1, 2, 4, 8, 16, 32"},
     {"ophase", &Tuning::ophase, -1, kRegionMax, nullptr, "ophase must be -1 (auto) .. 64"},
     {"order", &Tuning::order, -1, kRegionMax, nullptr,

@@ -27,6 +27,9 @@ struct Tuning {
   // L1 on 16-bit fixed-point codes of any train set at d <= 256 (metric 8,
   // knn_cand_fix16.hip): 0 off, 1 on at every batch size.  Opt-in: no auto.
   int u16l1 = 0;
+  // the same pass at 256 < d <= 1024 (knn_cand_fix16_wide.hip): 0 off, 1 on at
+  // every batch size.  Opt-in: no auto; "u16l1" moves no call above 256 dims.
+  int u16l1w = 0;
   int ties = 1;          // reference tie order: 0 off, 1 vote-affecting ties, 2 all ties
   int m16 = -1;          // bf16x3 on the 16x16x32 MFMA layout: -1 auto, 0 off, 1 on
   int64_t seed = 0;      // seeded thresholds: 0 / -1 off, N sample rows (experiment)
@@ -79,8 +82,9 @@ struct PlanIn {
 
 // the train image the candidate kernel reads (knn_api.cpp: ensure_*)
 // (IMG_I8W: the plain int8 rows of the wide L1-on-codes pass, d > 256;
-// IMG_U16: the 16-bit fixed-point rows of kernel metric 8)
-enum TrainImage { IMG_FP32, IMG_BF16X3, IMG_FP16, IMG_FP16_S3, IMG_I8, IMG_I8W, IMG_U16 };
+// IMG_U16: the 16-bit fixed-point rows of kernel metric 8; IMG_U16W: its
+// wide form's tiles of dim slabs, d > 256)
+enum TrainImage { IMG_FP32, IMG_BF16X3, IMG_FP16, IMG_FP16_S3, IMG_I8, IMG_I8W, IMG_U16, IMG_U16W };
 
 struct SearchPlan {
   bool ok;           // false: no kernel is instantiated for this geometry

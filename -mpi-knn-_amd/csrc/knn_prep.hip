@@ -601,13 +601,15 @@ void launch_prep_i8_rows(const double* X64, const double* cent, int64_t n, int d
                      DP, n_pad, s, out, perm);
 }
 
-// -------------------- 16-bit fixed-point L1 images (kernel metric 8, d <= 256)
+// ------------------------------ 16-bit fixed-point L1 images (kernel metric 8)
 // code = clamp(rint(2^e (v - mu)), -32768, 32767) + 32768 per dim, one scale
 // 2^e for all dims (knn_cand_fix16.hip; u16_code, knn_device.h).
 
 // Train rows: DP codes per row (0 in the pad dims and on pad rows), one wave
 // per row; the largest row sum of the coding errors |code - 32768 - 2^e (x -
 // mu)| (code units; fp64, non-negative -> ordered as u64 bits) into dmax.
+// WIDE: the tiles of dim slabs of knn_cand_fix16_wide.hip (knn_kernels.h).
+template <bool WIDE>
 __global__ void __launch_bounds__(256)
 prep_u16_train_kernel(const double* __restrict__ X64, const double* __restrict__ mu, int64_t n,
                       int d, int DP, int64_t n_pad, int e, unsigned short* __restrict__ out,
@@ -625,7 +627,15 @@ prep_u16_train_kernel(const double* __restrict__ X64, const double* __restrict__
         k = (unsigned short)(int)u16_code(X64[src * d + c], mu[c], e, er);
         dsum += er;
       }
-      out[row * DP + c] = k;
+      if (WIDE) {
+        const int cpr = DP >> 3, c0 = fix16_wide_slab0(cpr), ch = c >> 3;
+        const bool sl = ch >= c0;  // the chunk's slab: 32 rows of cw chunks
+        const int cw = sl ? cpr - c0 : c0;
+        const int64_t at = (row >> 5) * 32 * cpr + (sl ? 32 * c0 : 0) + (row & 31) * cw +
+                           (sl ? ch - c0 : ch);
+        out[at * 8 + (c & 7)] = k;
+      } else
+        out[row * DP + c] = k;
     }
     m = fmax(m, wave_sum_d(dsum));
   }
@@ -638,13 +648,24 @@ void launch_prep_u16_train(const double* X64, const double* mu, int64_t n, int d
                            hipStream_t s, const int* perm) {
   int64_t blocks = (n_pad + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(prep_u16_train_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X64, mu, n, d,
-                     DP, n_pad, e, out, dmax, perm);
+  hipLaunchKernelGGL(prep_u16_train_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, X64, mu,
+                     n, d, DP, n_pad, e, out, dmax, perm);
+}
+
+void launch_prep_u16_train_wide(const double* X64, const double* mu, int64_t n, int d, int DP,
+                                int64_t n_pad, int e, unsigned short* out,
+                                unsigned long long* dmax, hipStream_t s, const int* perm) {
+  int64_t blocks = (n_pad + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(prep_u16_train_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, X64, mu,
+                     n, d, DP, n_pad, e, out, dmax, perm);
 }
 
 // Query rows: the same codes; a query launch_query_check marked void or
 // non-finite (valid[row] <= 0) gets zero codes, i.e. finite proxies the merge
-// ignores.
+// ignores.  WIDE: the step-major code rows of knn_cand_fix16_wide.hip
+// (knn_kernels.h).
+template <bool WIDE>
 __global__ void __launch_bounds__(256)
 prep_u16_queries_kernel(const double* __restrict__ Q64, const double* __restrict__ mu, int64_t m,
                         int d, int DP, int64_t m_pad, int e, unsigned short* __restrict__ out,
@@ -659,7 +680,10 @@ prep_u16_queries_kernel(const double* __restrict__ Q64, const double* __restrict
       double er;
       k = (unsigned short)(int)u16_code(Q64[row * d + c], mu[c], e, er);
     }
-    out[i] = k;
+    if (WIDE)
+      out[(((row >> 5) * (DP >> 3) + (c >> 3)) * 32 + (row & 31)) * 8 + (c & 7)] = k;
+    else
+      out[i] = k;
   }
 }
 
@@ -668,8 +692,17 @@ void launch_prep_u16_queries(const double* Q64, const double* mu, int64_t m, int
                              hipStream_t s) {
   int64_t blocks = (m_pad * DP + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(prep_u16_queries_kernel, dim3((unsigned)blocks), dim3(256), 0, s, Q64, mu, m,
-                     d, DP, m_pad, e, out, valid);
+  hipLaunchKernelGGL(prep_u16_queries_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, Q64,
+                     mu, m, d, DP, m_pad, e, out, valid);
+}
+
+void launch_prep_u16_queries_wide(const double* Q64, const double* mu, int64_t m, int d, int DP,
+                                  int64_t m_pad, int e, unsigned short* out, const float* valid,
+                                  hipStream_t s) {
+  int64_t blocks = (m_pad * DP + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(prep_u16_queries_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, Q64,
+                     mu, m, d, DP, m_pad, e, out, valid);
 }
 
 __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {

@@ -16,7 +16,8 @@
 // seconds on stderr; stdout stays the reference's), --tune KEY=VALUE (a
 // tuning key of the library, knn_set_tuning; repeatable -- e.g. --tune i8l1=1
 // for the Manhattan pass on int8 codes of byte-valued CSVs, --tune u16l1=1
-// for the one on 16-bit fixed-point codes of any data, normalised included),
+// for the one on 16-bit fixed-point codes of any data, normalised included,
+// --tune u16l1w=1 for the same at 256 < dim <= 1024),
 // --K_list k1,k2,... (needs --Validation true): the validation pass scores
 // every K of the list from one search (knn_group_classify_sweep), prints
 // "K = <k> accuracy = <acc>" per K in list order, selects the first K whose
@@ -118,7 +119,8 @@ void usage() {
           "  --tune sets a tuning key of the library (knn_amd.h, knn_set_tuning), e.g.\n"
           "  --tune i8l1=1: the L1 pass on int8 codes for byte-coded data at dim <= 256\n"
           "  (i8l1=2: also at 256 < dim <= 1024); --tune u16l1=1: the L1 pass on 16-bit\n"
-          "  fixed-point codes for any data at dim <= 256 (--Normalize true included)\n"
+          "  fixed-point codes for any data at dim <= 256 (--Normalize true included);\n"
+          "  --tune u16l1w=1: the same at 256 < dim <= 1024 (the default dim = 784)\n"
           "  --csv gpu parses the CSV files on GPU 0 (same values as the default host reader)\n");
 }
 

@@ -769,7 +769,7 @@ class Classifier:
 
     def set_tuning(self, key, value):
         """Experiment overrides (knn_amd.h, knn_set_tuning): "R", "S", "nw",
-        "ablate", "fp16", "mfma16", "i8", "i8w", "i8l1", "u16l1", "gk", "s3q", "qres", "s3gq",
+        "ablate", "fp16", "mfma16", "i8", "i8w", "i8l1", "u16l1", "u16l1w", "gk", "s3q", "qres", "s3gq",
         "xhswz", "ties", "seed", "order", "ophase", "nblk"; 0 (or -1 where stated) =
         automatic.  "i8l1": L1 searches on the int8 codes of an
         integer-coded train set at d <= 256 (candidate path 7, v_sad_u8; results
@@ -779,7 +779,11 @@ class Classifier:
         searches at d <= 256 on 16-bit fixed-point codes of any train set
         (candidate path 8, v_sad_u16; certified, results unchanged) at every
         batch size, except where "i8l1" selects path 7; 0 (default) off; no
-        auto.  "order" and "nblk" shape the train layout and are read by
+        auto.  "u16l1w": 1 = the same pass at 256 < d <= 1024 (the wide
+        kernel, cand_fix16_wide_kernel; the sums' rounding to float is part of
+        the certified bound), except where "i8l1" = 2 selects path 7; 0
+        (default) off; no auto; "u16l1" moves no call above 256 dims.
+        "order" and "nblk" shape the train layout and are read by
         set_train: "order" -1 = region order only for integer-coded sets whose
         int8 image is <= 192 MB (n / 16384 regions, up to 64, at least 8),
         1 = n / 16384 regions (off below n = 32768); "nblk" -1 = norm blocks

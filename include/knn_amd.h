@@ -623,6 +623,13 @@ int knn_last_geometry(knn_ctx* ctx, int64_t out[4]);
  * unchanged.  Tuning key "u16l1": 0 off (the default), 1 on at every batch
  * size; opt-in only, AUTO never chooses it; where "i8l1" selects path 7 for
  * an integer-coded train set, that exact pass wins.
+ * The same pass serves 256 < d <= 1024 (the reference's default dim = 784
+ * with Normalize = true) in a wide form that re-reads the query codes per
+ * train tile (cand_fix16_wide_kernel).  Its integer sums reach 65535 x 1024 <
+ * 2^26 and are rounded once to float, off by at most 1 code unit up to 512
+ * padded dims and 2 up to 1024; that term is part of the certified bound, so
+ * results are unchanged.  Tuning key "u16l1w": 0 off (the default), 1 on at
+ * every batch size; opt-in only; "i8l1" = 2 wins for an integer-coded set.
  * Environment override at knn_create: KNN_PRECISION=fp32|bf16x3|fp16. */
 #define KNN_PRECISION_AUTO 0
 #define KNN_PRECISION_FP32 1
@@ -633,7 +640,8 @@ int knn_set_precision(knn_ctx* ctx, int mode);
  * L2 (32x32x16 MFMA), 3 bf16x3 L2 (16x16x32), 4 fp16 L2 (16x16x32), 5 int8
  * L2 (16x16x64, exact integer dot products), 6 int8 L2 (32x32x32), 7 L1 on
  * int8 codes (v_sad_u8, exact integer sums; d <= 256, or <= 1024 with "i8l1"
- * = 2), 8 L1 on 16-bit fixed-point codes (v_sad_u16, certified; d <= 256). */
+ * = 2), 8 L1 on 16-bit fixed-point codes (v_sad_u16, certified; d <= 256, or
+ * <= 1024 with "u16l1w" = 1). */
 int knn_last_candidate_path(knn_ctx* ctx);
 /* Name of the last candidate kernel launched, as rocprofv3 reports it
  * without namespace, spaces and argument list (e.g. "cand_kernel<128,4,4,8>"). */
@@ -653,7 +661,10 @@ const char* knn_last_kernel_name(knn_ctx* ctx);
  * beyond 1024 dims, off the grid or under L2 it plans what 0 plans), "u16l1"
  * (no auto: 0 off, the default; 1 the L1 pass on 16-bit fixed-point codes,
  * path 8, for any train set at d <= 256 and every batch size, except where
- * "i8l1" selects path 7; it moves no L2 call and no call at d > 256), "i8w" (int8
+ * "i8l1" selects path 7; it moves no L2 call and no call at d > 256), "u16l1w"
+ * (no auto: 0 off, the default; 1 that pass at 256 < d <= 1024 on the wide
+ * kernel, cand_fix16_wide_kernel, at every batch size, except where "i8l1" =
+ * 2 selects path 7; it moves no L2 call and no call at d <= 256), "i8w" (int8
  * kernel: -1 auto, 0 the 16x16x64 one, 1 the 32x32x32 one; also read by
  * knn_set_train*, whose norm blocks interleave the rows over that kernel's
  * lane lists -- set it before the train set: a later change keeps results
