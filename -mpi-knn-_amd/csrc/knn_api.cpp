@@ -76,6 +76,18 @@ static int device_guard(knn_ctx* ctx) {
   return KNN_OK;
 }
 
+// the stream a *_device call runs on: the caller's, or the context's own
+static hipStream_t stream_of(const knn_ctx* ctx, void* stream) {
+  return stream ? (hipStream_t)stream : ctx->stream;
+}
+
+// a host-API output: bytes from the staging buffer to dst where the caller
+// asked for it (dst nullable) and there is something to copy
+static int copy_back(void* dst, const void* src, size_t bytes, hipStream_t s) {
+  if (dst && bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+  return KNN_OK;
+}
+
 extern "C" {
 
 const char* knn_version(void) { return "mpi-knn-amd 0.1 (gfx950)"; }
@@ -1097,33 +1109,136 @@ static int check_query_args(knn_ctx* ctx, int64_t m, int32_t k, int32_t metric) 
   return KNN_OK;
 }
 
-// ---- per-class evaluation (knn_eval.hip)
-// The sweep (under exclusion with d_excl) into d_labels or, without them, the
-// context's workspace, then the confusion pass over those labels.  zero: the
-// call clears d_conf / d_unl first, as the sweep clears d_correct; the
-// leave-one-out host twin sums its batches on the device without it.
-static int sweep_eval(knn_ctx* ctx, const double* dQ, int64_t m, const int64_t* d_excl,
-                      const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
-                      const int32_t* d_truth, int64_t* d_correct, int64_t* d_conf, int64_t* d_unl,
-                      bool zero, hipStream_t s) {
+// ---- the K sweep's one body: plain, under row exclusion (knn_loo.hip) and
+// under group exclusion (knn_lgo.hip)
+
+// what a sweep's queries leave out of the train set
+struct Excl {
+  enum Kind { NONE, ROW, GROUP } kind = NONE;
+  const int64_t* row = nullptr;     // ROW: one global train index per query (-1 = none)
+  const int32_t* qgroup = nullptr;  // GROUP: one id of ctx->groups per query (-1 = none)
+  static Excl of_row(const int64_t* d_excl) {  // (a null array excludes nothing)
+    return d_excl ? Excl{ROW, d_excl, nullptr} : Excl{};
+  }
+  static Excl of_group(const int32_t* d_qgroup) {
+    return d_qgroup ? Excl{GROUP, nullptr, d_qgroup} : Excl{};
+  }
+};
+
+// knn_classify_sweep_device / _excl_device / _gexcl_device on stream s.  Under
+// exclusion a query may lose `drop` rows (1, or the largest group), so one
+// search at kmax + drop goes into internal rows and is compacted into the
+// kmax-entry rows of the reduced sets; the plain sweep searches at kmax
+// straight into those rows.
+static int sweep_run(knn_ctx* ctx, const double* dQ, int64_t m, const Excl& ex, const int32_t* ks,
+                     int32_t nk, int32_t metric, int32_t* d_labels, const int32_t* d_truth,
+                     int64_t* d_correct, int64_t* d_idx, double* d_dist, int32_t* d_flags,
+                     hipStream_t s) {
   int rc;
   if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  if (ex.kind == Excl::GROUP && !ctx->groups)
+    return knn_fail(KNN_ERR_STATE, "sweep under group exclusion before knn_set_groups");
+  const TrainDev& t = ctx->train;
+  const int drop = ex.kind == Excl::GROUP ? ctx->gmax : ex.kind == Excl::ROW ? 1 : 0;
   int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
-  if (!d_truth)
-    return knn_fail(KNN_ERR_ARG, "null d_truth (the evaluation needs the queries' true labels)");
+  if ((rc = knn_sweep_check_ks(ks, nk, t.n - drop, &kmax))) return rc;
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  if (m == 0) return KNN_OK;
+  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
+  const int* dks = (const int*)ctx->sw_ks.p;
+  if (kmax == 0) {  // every K is 0: no neighbour is read, max_label stays -1 (cpp:324)
+    launch_sweep_vote(nullptr, m, 0, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
+                      (unsigned long long*)d_correct, ctx->cu_count, s);
+    if (d_flags) launch_fill_i32(d_flags, m, 0, s);
+    HIP_TRY(hipGetLastError());
+    return KNN_OK;
+  }
+  const bool excl = ex.kind != Excl::NONE;
+  const int k1 = kmax + drop;  // <= n
+  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (excl && (rc = ctx->loo_idx.ensure((size_t)m * k1 * sizeof(int64_t)))) return rc;
+  if (excl && (rc = ctx->loo_dist.ensure((size_t)m * k1 * sizeof(double)))) return rc;
+  if (excl && (rc = ctx->loo_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
+  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
+  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
+  // the rows the sweep always keeps (idx, dist, flags), at kmax
+  Sink out{};
+  out.mode = MODE_SINGLE;
+  out.k = kmax;
+  out.idx_off = ctx->idx_off;
+  out.labels = (int32_t*)ctx->sw_lab.p;
+  out.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
+  out.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
+  out.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
+  out.tie_defer = 1;  // the search neither queues ties nor runs the reference-order pass
+  Sink sink = out;    // the rows the search writes
+  if (excl) {
+    sink.k = k1;
+    sink.idx = (int64_t*)ctx->loo_idx.p;
+    sink.dist = (double*)ctx->loo_dist.p;
+    sink.flags = (int32_t*)ctx->loo_flags.p;
+  }
+  const int W = (int)std::min<int64_t>((int64_t)k1 + 1, t.n);
+  rc = k1 > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
+                  : knn_run_search(ctx, dQ, m, W, metric, sink, s);
+  if (rc) return rc;
+  if (ex.kind == Excl::ROW)
+    launch_loo_drop(sink.dist, sink.idx, sink.flags, ex.row, m, kmax, t.lab, ctx->idx_off, t.n,
+                    out.dist, out.idx, out.flags, ctx->cu_count, s);
+  else if (ex.kind == Excl::GROUP)
+    launch_lgo_drop(sink.dist, sink.idx, sink.flags, ex.qgroup, ctx->groups, m, kmax, k1, t.lab,
+                    ctx->idx_off, t.n, out.dist, out.idx, out.flags, ctx->cu_count, s);
+  // queries whose label at some K of the list the reference's tie order could
+  // change -> the tie queue -> the reference-order pass over the whole top
+  // kmax (std::sort over each query's remaining records)
+  if (ctx->tune.ties) {
+    out.tie_mode = ctx->tune.ties;
+    TieScratch ts;
+    if ((rc = tie_setup(ctx, m, out, ts, true, s))) return rc;
+    launch_sweep_tie_scan(out.dist, out.idx, out.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
+                          out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
+    if (ex.kind == Excl::GROUP)
+      launch_tie_order_group(metric, t, dQ, out.tie_q, out.tie_cnt, ctx->class_cnt,
+                             (unsigned char*)ctx->tie_ws.p, ts.per, ts.nwg, out,
+                             (unsigned long long*)ctx->totals.p + 2, s, ex.qgroup, ctx->groups);
+    else
+      tie_order(ctx, ts, metric, dQ, out, s, ex.row);
+  }
+  sweep_votes(ctx, out.idx, out.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+  return KNN_OK;
+}
+
+// ---- per-class evaluation (knn_eval.hip)
+// The sweep into d_labels or, without them, the context's workspace, then the
+// confusion pass over those labels against d_truth (d_conf / d_unl nullable:
+// none asked for, no pass).  zero: the call clears d_conf / d_unl first, as
+// the sweep clears d_correct; the callers that walk the train set in batches
+// sum them on the device without it.
+static int sweep_eval_run(knn_ctx* ctx, const double* dQ, int64_t m, const Excl& ex,
+                          const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
+                          const int32_t* d_truth, int64_t* d_correct, int64_t* d_idx,
+                          double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl,
+                          bool zero, hipStream_t s) {
+  int rc;
   const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
-  if (zero && d_conf) HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)nk * cc * sizeof(int64_t), s));
-  if (zero && d_unl) HIP_TRY(hipMemsetAsync(d_unl, 0, (size_t)nk * sizeof(int64_t), s));
+  if (nk >= 1 && nk <= 4096) {  // (a bad nk is reported by the sweep's own check)
+    if (zero && d_conf) HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)nk * cc * sizeof(int64_t), s));
+    if (zero && d_unl) HIP_TRY(hipMemsetAsync(d_unl, 0, (size_t)nk * sizeof(int64_t), s));
+  }
   int32_t* L = d_labels;
   if (!L) {
-    const size_t cells = (size_t)std::max<int64_t>(m, 1) * nk;
+    const size_t cells = (size_t)std::max<int64_t>(m, 1) * (size_t)std::max(nk, 1);
     if ((rc = ctx->ev_lab.ensure(cells * sizeof(int32_t)))) return rc;
     L = (int32_t*)ctx->ev_lab.p;
   }
-  rc = knn_classify_sweep_excl_device(ctx, dQ, m, d_excl, ks, nk, metric, L,
-                                      d_correct ? d_truth : nullptr, d_correct, nullptr, nullptr,
-                                      nullptr, s);
+  rc = sweep_run(ctx, dQ, m, ex, ks, nk, metric, L, d_correct ? d_truth : nullptr, d_correct,
+                 d_idx, d_dist, d_flags, s);
   if (rc || m == 0 || (!d_conf && !d_unl)) return rc;
   launch_eval_confusion(L, nk, m, d_truth, ctx->class_cnt, (unsigned long long*)d_conf,
                         (unsigned long long*)d_unl, s);
@@ -1132,135 +1247,205 @@ static int sweep_eval(knn_ctx* ctx, const double* dQ, int64_t m, const int64_t* 
   return KNN_OK;
 }
 
-// leave-one-out over train rows [row0, row0 + rows): the rows are the queries,
-// each excludes itself and its own label is its truth
-int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
-                      int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_conf,
-                      int64_t* d_unl, bool zero, hipStream_t s) {
+// the query form (knn_classify_sweep_eval_device's body): d_truth required
+static int sweep_eval(knn_ctx* ctx, const double* dQ, int64_t m, const int64_t* d_excl,
+                      const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
+                      const int32_t* d_truth, int64_t* d_correct, int64_t* d_conf, int64_t* d_unl,
+                      hipStream_t s) {
   int rc;
-  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-one-out sweep before set_train");
+  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
+  if (!d_truth)
+    return knn_fail(KNN_ERR_ARG, "null d_truth (the evaluation needs the queries' true labels)");
+  return sweep_eval_run(ctx, dQ, m, Excl::of_row(d_excl), ks, nk, metric, d_labels, d_truth,
+                        d_correct, nullptr, nullptr, nullptr, d_conf, d_unl, true, s);
+}
+
+// leave-one-out (own_group false) / leave-group-out over train rows [row0,
+// row0 + rows): the rows are the queries, each excludes itself / its own
+// group and its own label is its truth
+int knn_sweep_rows(knn_ctx* ctx, int64_t row0, int64_t rows, bool own_group, const int32_t* ks,
+                   int32_t nk, int32_t metric, int32_t* d_labels, int64_t* d_correct,
+                   int64_t* d_idx, double* d_dist, int32_t* d_flags, int64_t* d_conf,
+                   int64_t* d_unl, bool zero, hipStream_t s) {
+  int rc;
+  if (!ctx->trained)
+    return knn_fail(KNN_ERR_STATE, own_group ? "leave-group-out sweep before set_train"
+                                             : "leave-one-out sweep before set_train");
+  if (own_group && !ctx->groups)
+    return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before knn_set_groups");
   const TrainDev& t = ctx->train;
   if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
     return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
                                      std::to_string(row0) + " + " + std::to_string(rows) +
                                      ") outside the train set [0, " + std::to_string(t.n) + ")");
-  if ((rc = ctx->loo_excl.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int64_t)))) return rc;
-  int64_t* excl = (int64_t*)ctx->loo_excl.p;
-  launch_loo_self(excl, rows, ctx->idx_off + row0, s);
+  // query i is train row row0 + i
+  const size_t r1 = (size_t)std::max<int64_t>(rows, 1);
+  Excl ex;
+  if (own_group) {
+    if ((rc = ctx->lgo_qg.ensure(r1 * sizeof(int32_t)))) return rc;
+    launch_lgo_self((int32_t*)ctx->lgo_qg.p, ctx->groups, rows, row0, s);
+    ex = Excl::of_group((const int32_t*)ctx->lgo_qg.p);
+  } else {
+    if ((rc = ctx->loo_excl.ensure(r1 * sizeof(int64_t)))) return rc;
+    launch_loo_self((int64_t*)ctx->loo_excl.p, rows, ctx->idx_off + row0, s);
+    ex = Excl::of_row((const int64_t*)ctx->loo_excl.p);
+  }
   HIP_TRY(hipGetLastError());
-  return sweep_eval(ctx, t.X64 + row0 * t.d, rows, excl, ks, nk, metric, d_labels, t.lab + row0,
-                    d_correct, d_conf, d_unl, zero, s);
+  return sweep_eval_run(ctx, t.X64 + row0 * t.d, rows, ex, ks, nk, metric, d_labels,
+                        t.lab + row0, d_correct, d_idx, d_dist, d_flags, d_conf, d_unl, zero, s);
 }
 
-// ---- K sweep under group exclusion / leave-group-out (knn_lgo.hip)
+// ---- the host twins: staging in the context's buffers on its own stream
 
-// knn_classify_sweep_gexcl_device's body on stream s (d_qgroup non-null)
-static int gexcl_sweep(knn_ctx* ctx, const double* dQ, int64_t m, const int32_t* d_qgroup,
-                       const int32_t* ks, int32_t nk, int32_t metric, int32_t* d_labels,
-                       const int32_t* d_truth, int64_t* d_correct, int64_t* d_idx, double* d_dist,
-                       int32_t* d_flags, hipStream_t s) {
+// knn_classify_sweep / knn_classify_sweep_eval after their argument checks:
+// queries and truth up, the sweep (eval: through sweep_eval), the outputs the
+// caller asked for down, one wait
+static int host_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks, int32_t nk,
+                      int32_t kmax, int32_t metric, bool eval, int32_t* out_labels,
+                      const int32_t* truth, int64_t* out_correct, int64_t* out_conf,
+                      int64_t* out_unl, int64_t* out_idx, double* out_dist, int32_t* out_flags) {
   int rc;
-  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
-  if (!ctx->groups)
-    return knn_fail(KNN_ERR_STATE, "sweep under group exclusion before knn_set_groups");
-  const TrainDev& t = ctx->train;
-  const int gmax = ctx->gmax;
-  int32_t kmax = 0;
-  // a whole group (at most gmax rows) may be taken out
-  if ((rc = knn_sweep_check_ks(ks, nk, t.n - gmax, &kmax))) return rc;
-  if (kmax == 0)  // every K is 0: no neighbour is read
-    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
-                                     d_idx, d_dist, d_flags, s);
-  if ((d_truth != nullptr) != (d_correct != nullptr))
-    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
-  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
-  if (m == 0) return KNN_OK;
-  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
-  const int* dks = (const int*)ctx->sw_ks.p;
-  // one search at kmax + gmax into internal rows (neither queues ties nor runs
-  // the reference-order pass), compacted into the caller's kmax-entry rows
-  const int k1 = kmax + gmax;  // <= n
-  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if ((rc = ctx->loo_idx.ensure((size_t)m * k1 * sizeof(int64_t)))) return rc;
-  if ((rc = ctx->loo_dist.ensure((size_t)m * k1 * sizeof(double)))) return rc;
-  if ((rc = ctx->loo_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
-  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
-  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  Sink sink{};
-  sink.mode = MODE_SINGLE;
-  sink.k = k1;
-  sink.idx_off = ctx->idx_off;
-  sink.labels = (int32_t*)ctx->sw_lab.p;
-  sink.idx = (int64_t*)ctx->loo_idx.p;
-  sink.dist = (double*)ctx->loo_dist.p;
-  sink.flags = (int32_t*)ctx->loo_flags.p;
-  sink.tie_defer = 1;
-  const int W = (int)std::min<int64_t>((int64_t)k1 + 1, t.n);
-  rc = k1 > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
-                  : knn_run_search(ctx, dQ, m, W, metric, sink, s);
-  if (rc) return rc;
-  Sink out = sink;  // the rows of the reduced sets, at kmax
-  out.k = kmax;
-  out.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
-  out.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
-  out.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
-  launch_lgo_drop(sink.dist, sink.idx, sink.flags, d_qgroup, ctx->groups, m, kmax, k1, t.lab,
-                  ctx->idx_off, t.n, out.dist, out.idx, out.flags, ctx->cu_count, s);
-  if (ctx->tune.ties) {  // the sweep's tie scan; std::sort over each query's remaining records
-    out.tie_mode = ctx->tune.ties;
-    TieScratch ts;
-    if ((rc = tie_setup(ctx, m, out, ts, true, s))) return rc;
-    launch_sweep_tie_scan(out.dist, out.idx, out.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
-                          out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
-    launch_tie_order_group(metric, t, dQ, out.tie_q, out.tie_cnt, ctx->class_cnt,
-                           (unsigned char*)ctx->tie_ws.p, ts.per, ts.nwg, out,
-                           (unsigned long long*)ctx->totals.p + 2, s, d_qgroup, ctx->groups);
+  const int d = ctx->train.d;
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  const size_t m1 = (size_t)std::max<int64_t>(m, 1), mk = (size_t)m * kmax;
+  if ((rc = ctx->Q64.ensure(m1 * d * sizeof(double)))) return rc;
+  if (out_labels && (rc = ctx->sw_out.ensure(m1 * nk * sizeof(int32_t)))) return rc;
+  if (truth && (rc = ctx->sw_truth.ensure(m1 * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_idx && (rc = ctx->o_idx.ensure(mk * sizeof(int64_t)))) return rc;
+  if (out_dist && (rc = ctx->o_dist.ensure(mk * sizeof(double)))) return rc;
+  if (out_flags && (rc = ctx->o_flags.ensure(m1 * sizeof(int32_t)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (m > 0) {
+    HIP_TRY(hipMemcpyAsync(ctx->Q64.p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, s));
+    if (truth)
+      HIP_TRY(hipMemcpyAsync(ctx->sw_truth.p, truth, (size_t)m * sizeof(int32_t),
+                             hipMemcpyHostToDevice, s));
   }
-  sweep_votes(ctx, out.idx, out.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
+  const double* dQ = (const double*)ctx->Q64.p;
+  int32_t* d_labels = out_labels ? (int32_t*)ctx->sw_out.p : nullptr;
+  const int32_t* d_truth = truth ? (const int32_t*)ctx->sw_truth.p : nullptr;
+  int64_t* d_correct = out_correct ? (int64_t*)ctx->sw_corr.p : nullptr;
+  if (eval)
+    rc = sweep_eval(ctx, dQ, m, nullptr, ks, nk, metric, d_labels, d_truth, d_correct,
+                    out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
+                    out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, s);
+  else
+    rc = sweep_run(ctx, dQ, m, Excl{}, ks, nk, metric, d_labels, d_truth, d_correct,
+                   out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
+                   out_dist ? (double*)ctx->o_dist.p : nullptr,
+                   out_flags ? (int32_t*)ctx->o_flags.p : nullptr, s);
+  if (rc) return rc;
+  if ((rc = copy_back(out_labels, ctx->sw_out.p, (size_t)m * nk * sizeof(int32_t), s))) return rc;
+  if ((rc = copy_back(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_flags, ctx->o_flags.p, (size_t)m * sizeof(int32_t), s))) return rc;
+  if ((rc = copy_back(out_idx, ctx->o_idx.p, mk * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_dist, ctx->o_dist.p, mk * sizeof(double), s))) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
   return KNN_OK;
 }
 
-// leave-group-out over train rows [row0, row0 + rows): the rows are the
-// queries, each excludes its own group and its own label is its truth
-int knn_lgo_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
-                 int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
-                 double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl, bool zero,
-                 hipStream_t s) {
+// knn_loo_sweep / knn_loo_sweep_eval / knn_lgo_sweep after their argument
+// checks: knn_sweep_rows over the whole train set in fixed batches (the
+// workspace does not grow with n; without out_labels no [nk][n] array exists
+// anywhere).  conf / unl are summed over the batches on the device, correct
+// on the host.
+static int host_rows_walk(knn_ctx* ctx, bool own_group, const int32_t* ks, int32_t nk,
+                          int32_t kmax, int32_t metric, int32_t* out_labels,
+                          int64_t* out_correct, int64_t* out_conf, int64_t* out_unl,
+                          int64_t* out_idx, double* out_dist, int32_t* out_flags) {
   int rc;
-  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before set_train");
-  if (!ctx->groups) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before knn_set_groups");
-  const TrainDev& t = ctx->train;
-  if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
-    return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
-                                     std::to_string(row0) + " + " + std::to_string(rows) +
-                                     ") outside the train set [0, " + std::to_string(t.n) + ")");
+  const int64_t n = ctx->train.n;
+  const int64_t B = std::min<int64_t>(n, 16384);
+  const int64_t nb = (n + B - 1) / B;
+  const size_t bk = (size_t)B * kmax;
   const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
-  if (nk >= 1 && nk <= 4096) {  // (a bad nk is reported by the sweep's own check)
-    if (zero && d_conf) HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)nk * cc * sizeof(int64_t), s));
-    if (zero && d_unl) HIP_TRY(hipMemsetAsync(d_unl, 0, (size_t)nk * sizeof(int64_t), s));
+  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if (out_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
+  if (out_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
+  if (out_flags && (rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (out_conf) HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+  if (out_unl) HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
+  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);  // per batch, summed at the end
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t r0 = b * B, rows = std::min(B, n - r0);
+    rc = knn_sweep_rows(ctx, r0, rows, own_group, ks, nk, metric, (int32_t*)ctx->sw_out.p,
+                        out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
+                        out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
+                        out_dist ? (double*)ctx->o_dist.p : nullptr,
+                        out_flags ? (int32_t*)ctx->o_flags.p : nullptr,
+                        out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
+                        out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, false, s);
+    if (rc) return rc;
+    // the batch's labels [nk][rows] -> columns [r0, r0 + rows) of [nk][n]
+    if (out_labels)
+      HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
+                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
+                               (size_t)nk, hipMemcpyDeviceToHost, s));
+    if ((rc = copy_back(out_correct ? hc.data() + b * nk : nullptr, ctx->sw_corr.p,
+                        (size_t)nk * sizeof(int64_t), s)))
+      return rc;
+    if ((rc = copy_back(out_flags ? out_flags + r0 : nullptr, ctx->o_flags.p,
+                        (size_t)rows * sizeof(int32_t), s)))
+      return rc;
+    if ((rc = copy_back(out_idx ? out_idx + r0 * kmax : nullptr, ctx->o_idx.p,
+                        (size_t)rows * kmax * sizeof(int64_t), s)))
+      return rc;
+    if ((rc = copy_back(out_dist ? out_dist + r0 * kmax : nullptr, ctx->o_dist.p,
+                        (size_t)rows * kmax * sizeof(double), s)))
+      return rc;
   }
-  int32_t* L = d_labels;
-  if (!L) {
-    if (!d_conf && !d_unl) return knn_fail(KNN_ERR_ARG, "null labels output");
-    const size_t cells = (size_t)std::max<int64_t>(rows, 1) * (size_t)std::max(nk, 1);
-    if ((rc = ctx->ev_lab.ensure(cells * sizeof(int32_t)))) return rc;
-    L = (int32_t*)ctx->ev_lab.p;
-  }
-  if ((rc = ctx->lgo_qg.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int32_t)))) return rc;
-  int32_t* qg = (int32_t*)ctx->lgo_qg.p;
-  launch_lgo_self(qg, ctx->groups, rows, row0, s);  // query i is train row row0 + i
-  HIP_TRY(hipGetLastError());
-  rc = gexcl_sweep(ctx, t.X64 + row0 * t.d, rows, qg, ks, nk, metric, L,
-                   d_correct ? t.lab + row0 : nullptr, d_correct, d_idx, d_dist, d_flags, s);
-  if (rc || rows == 0 || (!d_conf && !d_unl)) return rc;
-  launch_eval_confusion(L, nk, rows, t.lab + row0, ctx->class_cnt, (unsigned long long*)d_conf,
-                        (unsigned long long*)d_unl, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the confusion pass
+  if ((rc = copy_back(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t), s))) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_correct)
+    for (int32_t j = 0; j < nk; j++) {
+      out_correct[j] = 0;
+      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
+    }
+  return KNN_OK;
+}
+
+// ---- votes over caller-supplied rows (knn_sweep.hip, knn_eval.hip, knn_wvote.hip)
+
+// knn_vote_sweep_device / knn_vote_sweep_weighted_device up to the launch:
+// the argument checks, then the list of K and the zeroed counts on stream s
+static int vote_sweep_begin(knn_ctx* ctx, int64_t m, int32_t kmax, const int32_t* ks, int32_t nk,
+                            int32_t* d_labels, const int32_t* d_truth, int64_t* d_correct,
+                            hipStream_t s) {
+  int rc;
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  int32_t top = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, kmax, &top))) return rc;
+  if ((d_truth != nullptr) != (d_correct != nullptr))
+    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  return sweep_upload(ctx, ks, nk, d_correct, s);
+}
+
+// knn_vote_counts_device / knn_vote_weights_device: the geometry of one vote
+// over the first k entries of rows [m][kmax], and the output `what`
+static int check_vote_args(int64_t m, int32_t kmax, int32_t k, int32_t class_cnt, const void* out,
+                           const char* what) {
+  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
+  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
+  if (k < 0) return knn_fail(KNN_ERR_ARG, "k must be >= 0");
+  if (k > kmax)
+    return knn_fail(KNN_ERR_ARG, "k = " + std::to_string(k) + " exceeds kmax = " +
+                                     std::to_string(kmax) + " (the entries of a row)");
+  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
+  if (!out) return knn_fail(KNN_ERR_ARG, std::string("null ") + what);
   return KNN_OK;
 }
 
@@ -1273,7 +1458,7 @@ int knn_classify_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t k, in
   if ((rc = device_guard(ctx))) return rc;
   if ((rc = check_query_args(ctx, m, k, metric))) return rc;
   if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   if (m == 0) return KNN_OK;
   if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
   if (k == 0) {  // cpp:324: max_label stays -1
@@ -1335,17 +1520,10 @@ int knn_classify(knn_ctx* ctx, const double* Q, int64_t m, int32_t k, int32_t me
                            out_dist ? (double*)ctx->o_dist.p : nullptr,
                            (int32_t*)ctx->o_flags.p, s);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out_labels, ctx->o_lab.p, (size_t)m * sizeof(int32_t),
-                         hipMemcpyDeviceToHost, s));
-  if (out_flags)
-    HIP_TRY(hipMemcpyAsync(out_flags, ctx->o_flags.p, (size_t)m * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_idx && k > 0)
-    HIP_TRY(hipMemcpyAsync(out_idx, ctx->o_idx.p, (size_t)m * k * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_dist && k > 0)
-    HIP_TRY(hipMemcpyAsync(out_dist, ctx->o_dist.p, (size_t)m * k * sizeof(double),
-                           hipMemcpyDeviceToHost, s));
+  if ((rc = copy_back(out_labels, ctx->o_lab.p, (size_t)m * sizeof(int32_t), s))) return rc;
+  if ((rc = copy_back(out_flags, ctx->o_flags.p, (size_t)m * sizeof(int32_t), s))) return rc;
+  if ((rc = copy_back(out_idx, ctx->o_idx.p, (size_t)m * k * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_dist, ctx->o_dist.p, (size_t)m * k * sizeof(double), s))) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   return KNN_OK;
 }
@@ -1356,15 +1534,8 @@ int knn_vote_sweep_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_t
                           void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
-  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
-  int32_t top = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, kmax, &top))) return rc;
-  if ((d_truth != nullptr) != (d_correct != nullptr))
-    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
-  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  hipStream_t s = stream_of(ctx, stream);
+  if ((rc = vote_sweep_begin(ctx, m, kmax, ks, nk, d_labels, d_truth, d_correct, s))) return rc;
   if (m == 0) return KNN_OK;
   if (kmax > 0 && (!d_idx || !d_lab)) return knn_fail(KNN_ERR_ARG, "null neighbour rows / labels");
   launch_sweep_vote(d_idx, m, kmax, d_lab, idx_base, (const int*)ctx->sw_ks.p, nk, d_labels,
@@ -1379,58 +1550,8 @@ int knn_classify_sweep_device(knn_ctx* ctx, const double* dQ, int64_t m, const i
                               double* d_dist, int32_t* d_flags, void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
-  int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
-  if ((d_truth != nullptr) != (d_correct != nullptr))
-    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
-  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
-  if (m == 0) return KNN_OK;
-  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
-  const TrainDev& t = ctx->train;
-  const int* dks = (const int*)ctx->sw_ks.p;
-  if (kmax == 0) {  // every K is 0: max_label stays -1 (cpp:324)
-    launch_sweep_vote(nullptr, m, 0, t.lab, ctx->idx_off, dks, nk, d_labels, d_truth,
-                      (unsigned long long*)d_correct, ctx->cu_count, s);
-    if (d_flags) launch_fill_i32(d_flags, m, 0, s);
-    HIP_TRY(hipGetLastError());
-    return KNN_OK;
-  }
-  // one search at kmax into rows the sweep always keeps (idx, dist, flags);
-  // the search neither queues ties nor runs the reference-order pass
-  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
-  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
-  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  Sink sink{};
-  sink.mode = MODE_SINGLE;
-  sink.k = kmax;
-  sink.idx_off = ctx->idx_off;
-  sink.labels = (int32_t*)ctx->sw_lab.p;
-  sink.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
-  sink.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
-  sink.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
-  sink.tie_defer = 1;
-  const int W = (int)std::min<int64_t>((int64_t)kmax + 1, t.n);
-  rc = kmax > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
-                    : knn_run_search(ctx, dQ, m, W, metric, sink, s);
-  if (rc) return rc;
-  // queries whose label at some K of the list the reference's tie order could
-  // change -> the tie queue -> the reference-order pass over the whole top kmax
-  if (ctx->tune.ties) {
-    sink.tie_mode = ctx->tune.ties;
-    TieScratch ts;
-    if ((rc = tie_setup(ctx, m, sink, ts, true, s))) return rc;
-    launch_sweep_tie_scan(sink.dist, sink.idx, sink.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
-                          sink.tie_mode, sink.tie_q, sink.tie_cnt, ctx->cu_count, s);
-    tie_order(ctx, ts, metric, dQ, sink, s);
-  }
-  sweep_votes(ctx, sink.idx, sink.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
-  return KNN_OK;
+  return sweep_run(ctx, dQ, m, Excl{}, ks, nk, metric, d_labels, d_truth, d_correct, d_idx,
+                   d_dist, d_flags, stream_of(ctx, stream));
 }
 
 int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks, int32_t nk,
@@ -1446,47 +1567,8 @@ int knn_classify_sweep(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* 
     return knn_fail(KNN_ERR_ARG, "truth and out_correct go together (both or neither)");
   if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
   if (m > 0 && !Q) return knn_fail(KNN_ERR_ARG, "null query pointer");
-  const int d = ctx->train.d;
-  const size_t mk = (size_t)m * std::max(kmax, 1);
-  if ((rc = ctx->Q64.ensure((size_t)m * d * sizeof(double)))) return rc;
-  if ((rc = ctx->sw_out.ensure((size_t)m * nk * sizeof(int32_t)))) return rc;
-  if ((rc = ctx->o_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if (truth && (rc = ctx->sw_truth.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if (truth && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_idx && (rc = ctx->o_idx.ensure(mk * sizeof(int64_t)))) return rc;
-  if (out_dist && (rc = ctx->o_dist.ensure(mk * sizeof(double)))) return rc;
-  hipStream_t s = ctx->stream;
-  if (m > 0) {
-    HIP_TRY(hipMemcpyAsync(ctx->Q64.p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, s));
-    if (truth)
-      HIP_TRY(hipMemcpyAsync(ctx->sw_truth.p, truth, (size_t)m * sizeof(int32_t),
-                             hipMemcpyHostToDevice, s));
-  }
-  rc = knn_classify_sweep_device(ctx, (const double*)ctx->Q64.p, m, ks, nk, metric,
-                                 (int32_t*)ctx->sw_out.p,
-                                 truth ? (const int32_t*)ctx->sw_truth.p : nullptr,
-                                 truth ? (int64_t*)ctx->sw_corr.p : nullptr,
-                                 out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
-                                 out_dist ? (double*)ctx->o_dist.p : nullptr,
-                                 (int32_t*)ctx->o_flags.p, s);
-  if (rc) return rc;
-  if (m > 0)
-    HIP_TRY(hipMemcpyAsync(out_labels, ctx->sw_out.p, (size_t)m * nk * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_correct)
-    HIP_TRY(hipMemcpyAsync(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_flags && m > 0)
-    HIP_TRY(hipMemcpyAsync(out_flags, ctx->o_flags.p, (size_t)m * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_idx && m > 0 && kmax > 0)
-    HIP_TRY(hipMemcpyAsync(out_idx, ctx->o_idx.p, (size_t)m * kmax * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_dist && m > 0 && kmax > 0)
-    HIP_TRY(hipMemcpyAsync(out_dist, ctx->o_dist.p, (size_t)m * kmax * sizeof(double),
-                           hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return KNN_OK;
+  return host_sweep(ctx, Q, m, ks, nk, kmax, metric, false, out_labels, truth, out_correct,
+                    nullptr, nullptr, out_idx, out_dist, out_flags);
 }
 
 // ---- K sweep under exclusion / leave-one-out (knn_loo.hip, cpp:308-343 with
@@ -1497,68 +1579,10 @@ int knn_classify_sweep_excl_device(knn_ctx* ctx, const double* dQ, int64_t m,
                                    int32_t metric, int32_t* d_labels, const int32_t* d_truth,
                                    int64_t* d_correct, int64_t* d_idx, double* d_dist,
                                    int32_t* d_flags, void* stream) {
-  if (!d_excl)  // nothing excluded for any query: the plain sweep
-    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
-                                     d_idx, d_dist, d_flags, stream);
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if ((rc = check_query_args(ctx, m, 0, metric))) return rc;
-  const TrainDev& t = ctx->train;
-  int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, t.n - 1, &kmax))) return rc;  // one row may be taken out
-  if (kmax == 0)  // every K is 0: no neighbour is read
-    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
-                                     d_idx, d_dist, d_flags, stream);
-  if ((d_truth != nullptr) != (d_correct != nullptr))
-    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
-  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
-  if (m == 0) return KNN_OK;
-  if (!dQ) return knn_fail(KNN_ERR_ARG, "null query pointer");
-  const int* dks = (const int*)ctx->sw_ks.p;
-  // one search at kmax + 1 into internal rows (neither queues ties nor runs
-  // the reference-order pass), compacted into the caller's kmax-entry rows
-  const int k1 = kmax + 1;
-  if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if ((rc = ctx->loo_idx.ensure((size_t)m * k1 * sizeof(int64_t)))) return rc;
-  if ((rc = ctx->loo_dist.ensure((size_t)m * k1 * sizeof(double)))) return rc;
-  if ((rc = ctx->loo_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  if (!d_idx && (rc = ctx->sw_idx.ensure((size_t)m * kmax * sizeof(int64_t)))) return rc;
-  if (!d_dist && (rc = ctx->sw_dist.ensure((size_t)m * kmax * sizeof(double)))) return rc;
-  if (!d_flags && (rc = ctx->sw_flags.ensure((size_t)m * sizeof(int32_t)))) return rc;
-  Sink sink{};
-  sink.mode = MODE_SINGLE;
-  sink.k = k1;
-  sink.idx_off = ctx->idx_off;
-  sink.labels = (int32_t*)ctx->sw_lab.p;
-  sink.idx = (int64_t*)ctx->loo_idx.p;
-  sink.dist = (double*)ctx->loo_dist.p;
-  sink.flags = (int32_t*)ctx->loo_flags.p;
-  sink.tie_defer = 1;
-  const int W = (int)std::min<int64_t>((int64_t)kmax + 2, t.n);
-  rc = k1 > kMaxK ? run_large_k(ctx, dQ, m, W, metric, sink, s)
-                  : knn_run_search(ctx, dQ, m, W, metric, sink, s);
-  if (rc) return rc;
-  Sink out = sink;  // the rows of the reduced sets, at kmax
-  out.k = kmax;
-  out.idx = d_idx ? d_idx : (int64_t*)ctx->sw_idx.p;
-  out.dist = d_dist ? d_dist : (double*)ctx->sw_dist.p;
-  out.flags = d_flags ? d_flags : (int32_t*)ctx->sw_flags.p;
-  launch_loo_drop(sink.dist, sink.idx, sink.flags, d_excl, m, kmax, t.lab, ctx->idx_off, t.n,
-                  out.dist, out.idx, out.flags, ctx->cu_count, s);
-  if (ctx->tune.ties) {  // the sweep's tie scan; std::sort over each query's remaining records
-    out.tie_mode = ctx->tune.ties;
-    TieScratch ts;
-    if ((rc = tie_setup(ctx, m, out, ts, true, s))) return rc;
-    launch_sweep_tie_scan(out.dist, out.idx, out.flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
-                          out.tie_mode, out.tie_q, out.tie_cnt, ctx->cu_count, s);
-    tie_order(ctx, ts, metric, dQ, out, s, d_excl);
-  }
-  sweep_votes(ctx, out.idx, out.dist, m, kmax, dks, nk, d_labels, d_truth, d_correct, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->done_ev, s));  // the call ends after the vote
-  return KNN_OK;
+  return sweep_run(ctx, dQ, m, Excl::of_row(d_excl), ks, nk, metric, d_labels, d_truth,
+                   d_correct, d_idx, d_dist, d_flags, stream_of(ctx, stream));
 }
 
 int knn_loo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
@@ -1566,20 +1590,9 @@ int knn_loo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t
                          double* d_dist, int32_t* d_flags, void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "leave-one-out sweep before set_train");
-  const TrainDev& t = ctx->train;
-  if (row0 < 0 || rows < 0 || row0 > t.n || rows > t.n - row0)
-    return knn_fail(KNN_ERR_ARG, "rows [" + std::to_string(row0) + ", " +
-                                     std::to_string(row0) + " + " + std::to_string(rows) +
-                                     ") outside the train set [0, " + std::to_string(t.n) + ")");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if ((rc = ctx->loo_excl.ensure((size_t)std::max<int64_t>(rows, 1) * sizeof(int64_t)))) return rc;
-  int64_t* excl = (int64_t*)ctx->loo_excl.p;
-  launch_loo_self(excl, rows, ctx->idx_off + row0, s);  // query i is train row row0 + i
-  HIP_TRY(hipGetLastError());
-  return knn_classify_sweep_excl_device(ctx, t.X64 + row0 * t.d, rows, excl, ks, nk, metric,
-                                        d_labels, d_correct ? t.lab + row0 : nullptr, d_correct,
-                                        d_idx, d_dist, d_flags, s);
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  return knn_sweep_rows(ctx, row0, rows, false, ks, nk, metric, d_labels, d_correct, d_idx, d_dist,
+                        d_flags, nullptr, nullptr, true, stream_of(ctx, stream));
 }
 
 int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
@@ -1587,54 +1600,13 @@ int knn_loo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, i
   int rc;
   if ((rc = device_guard(ctx))) return rc;
   if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
-  const int64_t n = ctx->train.n;
   int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n - 1, &kmax))) return rc;
   if (!out_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  // fixed batches: the workspace does not grow with n
-  const int64_t B = std::min<int64_t>(n, 16384);
-  const int64_t nb = (n + B - 1) / B;
-  const size_t bk = (size_t)B * std::max(kmax, 1);
-  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
-  if ((rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
-  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
-  if (out_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
-  hipStream_t s = ctx->stream;
-  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);  // per batch, summed at the end
-  for (int64_t b = 0; b < nb; b++) {
-    const int64_t r0 = b * B, rows = std::min(B, n - r0);
-    rc = knn_loo_sweep_device(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
-                              out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
-                              out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
-                              out_dist ? (double*)ctx->o_dist.p : nullptr,
-                              (int32_t*)ctx->o_flags.p, s);
-    if (rc) return rc;
-    // the batch's labels [nk][rows] -> columns [r0, r0 + rows) of [nk][n]
-    HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
-                             (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
-                             (size_t)nk, hipMemcpyDeviceToHost, s));
-    if (out_correct)
-      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
-                             hipMemcpyDeviceToHost, s));
-    if (out_flags)
-      HIP_TRY(hipMemcpyAsync(out_flags + r0, ctx->o_flags.p, (size_t)rows * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, s));
-    if (out_idx && kmax > 0)
-      HIP_TRY(hipMemcpyAsync(out_idx + r0 * kmax, ctx->o_idx.p,
-                             (size_t)rows * kmax * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (out_dist && kmax > 0)
-      HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
-                             (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (out_correct)
-    for (int32_t j = 0; j < nk; j++) {
-      out_correct[j] = 0;
-      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
-    }
-  return KNN_OK;
+  return host_rows_walk(ctx, false, ks, nk, kmax, metric, out_labels, out_correct, nullptr,
+                        nullptr, out_idx, out_dist, out_flags);
 }
+
 
 // ---- K sweep under group exclusion / leave-group-out (knn_lgo.hip)
 
@@ -1700,14 +1672,10 @@ int knn_classify_sweep_gexcl_device(knn_ctx* ctx, const double* dQ, int64_t m,
                                     int32_t metric, int32_t* d_labels, const int32_t* d_truth,
                                     int64_t* d_correct, int64_t* d_idx, double* d_dist,
                                     int32_t* d_flags, void* on_stream) {
-  if (!d_qgroup)  // nothing excluded for any query: the plain sweep
-    return knn_classify_sweep_device(ctx, dQ, m, ks, nk, metric, d_labels, d_truth, d_correct,
-                                     d_idx, d_dist, d_flags, on_stream);
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  hipStream_t s = on_stream ? (hipStream_t)on_stream : ctx->stream;
-  return gexcl_sweep(ctx, dQ, m, d_qgroup, ks, nk, metric, d_labels, d_truth, d_correct, d_idx,
-                     d_dist, d_flags, s);
+  return sweep_run(ctx, dQ, m, Excl::of_group(d_qgroup), ks, nk, metric, d_labels, d_truth,
+                   d_correct, d_idx, d_dist, d_flags, stream_of(ctx, on_stream));
 }
 
 int knn_lgo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
@@ -1715,10 +1683,9 @@ int knn_lgo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t
                          double* d_dist, int32_t* d_flags, void* on_stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  hipStream_t s = on_stream ? (hipStream_t)on_stream : ctx->stream;
   if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  return knn_lgo_rows(ctx, row0, rows, ks, nk, metric, d_labels, d_correct, d_idx, d_dist, d_flags,
-                      nullptr, nullptr, true, s);
+  return knn_sweep_rows(ctx, row0, rows, true, ks, nk, metric, d_labels, d_correct, d_idx, d_dist,
+                        d_flags, nullptr, nullptr, true, stream_of(ctx, on_stream));
 }
 
 int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
@@ -1728,68 +1695,13 @@ int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, i
   if ((rc = device_guard(ctx))) return rc;
   if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
   if (!ctx->groups) return knn_fail(KNN_ERR_STATE, "leave-group-out sweep before knn_set_groups");
-  const int64_t n = ctx->train.n;
   int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, n - ctx->gmax, &kmax))) return rc;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n - ctx->gmax, &kmax))) return rc;
   if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
-  // fixed batches: the workspace does not grow with n
-  const int64_t B = std::min<int64_t>(n, 16384);
-  const int64_t nb = (n + B - 1) / B;
-  const size_t bk = (size_t)B * std::max(kmax, 1);
-  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
-  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
-  if ((rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
-  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
-  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
-  if (out_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
-  hipStream_t s = ctx->stream;
-  // conf / unl are summed over the batches on the device, correct on the host
-  if (out_conf) HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
-  if (out_unl) HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
-  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);  // per batch, summed at the end
-  for (int64_t b = 0; b < nb; b++) {
-    const int64_t r0 = b * B, rows = std::min(B, n - r0);
-    rc = knn_lgo_rows(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
-                      out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
-                      out_idx ? (int64_t*)ctx->o_idx.p : nullptr,
-                      out_dist ? (double*)ctx->o_dist.p : nullptr, (int32_t*)ctx->o_flags.p,
-                      out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
-                      out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, false, s);
-    if (rc) return rc;
-    // the batch's labels [nk][rows] -> columns [r0, r0 + rows) of [nk][n]
-    if (out_labels)
-      HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
-                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
-                               (size_t)nk, hipMemcpyDeviceToHost, s));
-    if (out_correct)
-      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
-                             hipMemcpyDeviceToHost, s));
-    if (out_flags)
-      HIP_TRY(hipMemcpyAsync(out_flags + r0, ctx->o_flags.p, (size_t)rows * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, s));
-    if (out_idx && kmax > 0)
-      HIP_TRY(hipMemcpyAsync(out_idx + r0 * kmax, ctx->o_idx.p,
-                             (size_t)rows * kmax * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (out_dist && kmax > 0)
-      HIP_TRY(hipMemcpyAsync(out_dist + r0 * kmax, ctx->o_dist.p,
-                             (size_t)rows * kmax * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  if (out_conf)
-    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_unl)
-    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (out_correct)
-    for (int32_t j = 0; j < nk; j++) {
-      out_correct[j] = 0;
-      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
-    }
-  return KNN_OK;
+  return host_rows_walk(ctx, true, ks, nk, kmax, metric, out_labels, out_correct, out_conf,
+                        out_unl, out_idx, out_dist, out_flags);
 }
+
 
 // ---- per-class evaluation (knn_eval.hip): the confusion matrix at every K
 // of a sweep, the vote counts of ordered neighbour rows
@@ -1807,7 +1719,7 @@ int knn_confusion_device(knn_ctx* ctx, const int32_t* d_labels, int32_t nk, int6
   if (m == 0) return KNN_OK;
   if (!d_truth) return knn_fail(KNN_ERR_ARG, "null d_truth");
   if (!d_labels) return knn_fail(KNN_ERR_ARG, "null d_labels");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   launch_eval_confusion(d_labels, nk, m, d_truth, class_cnt, (unsigned long long*)d_conf,
                         (unsigned long long*)d_unl, s);
   HIP_TRY(hipGetLastError());
@@ -1819,19 +1731,11 @@ int knn_vote_counts_device(knn_ctx* ctx, const int64_t* d_idx, int64_t m, int32_
                            int32_t* d_counts, void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
-  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
-  if (k < 0) return knn_fail(KNN_ERR_ARG, "k must be >= 0");
-  if (k > kmax)
-    return knn_fail(KNN_ERR_ARG, "k = " + std::to_string(k) + " exceeds kmax = " +
-                                     std::to_string(kmax) + " (the entries of a row)");
-  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
-  if (!d_counts) return knn_fail(KNN_ERR_ARG, "null d_counts");
+  if ((rc = check_vote_args(m, kmax, k, class_cnt, d_counts, "d_counts"))) return rc;
   if (m == 0) return KNN_OK;
   if (k > 0 && (!d_idx || !d_lab)) return knn_fail(KNN_ERR_ARG, "null neighbour rows / labels");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   HIP_TRY(launch_eval_vote_counts(d_idx, m, kmax, d_lab, idx_base, k, class_cnt, d_counts,
-                                  ctx->cu_count, s));
+                                  ctx->cu_count, stream_of(ctx, stream)));
   HIP_TRY(hipGetLastError());
   return KNN_OK;
 }
@@ -1845,15 +1749,8 @@ int knn_vote_sweep_weighted_device(knn_ctx* ctx, const int64_t* d_idx, const dou
                                    void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
-  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
-  int32_t top = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, kmax, &top))) return rc;
-  if ((d_truth != nullptr) != (d_correct != nullptr))
-    return knn_fail(KNN_ERR_ARG, "d_truth and d_correct go together (both or neither)");
-  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  hipStream_t s = stream_of(ctx, stream);
+  if ((rc = vote_sweep_begin(ctx, m, kmax, ks, nk, d_labels, d_truth, d_correct, s))) return rc;
   if (m == 0) return KNN_OK;
   if (kmax > 0 && (!d_idx || !d_dist || !d_lab))
     return knn_fail(KNN_ERR_ARG, "null neighbour rows / distances / labels");
@@ -1868,20 +1765,12 @@ int knn_vote_weights_device(knn_ctx* ctx, const int64_t* d_idx, const double* d_
                             int32_t class_cnt, double* d_wsum, void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "m must be in [0, 2^31)");
-  if (kmax < 0) return knn_fail(KNN_ERR_ARG, "kmax must be >= 0");
-  if (k < 0) return knn_fail(KNN_ERR_ARG, "k must be >= 0");
-  if (k > kmax)
-    return knn_fail(KNN_ERR_ARG, "k = " + std::to_string(k) + " exceeds kmax = " +
-                                     std::to_string(kmax) + " (the entries of a row)");
-  if (class_cnt <= 0) return knn_fail(KNN_ERR_ARG, "class_cnt must be > 0");
-  if (!d_wsum) return knn_fail(KNN_ERR_ARG, "null d_wsum");
+  if ((rc = check_vote_args(m, kmax, k, class_cnt, d_wsum, "d_wsum"))) return rc;
   if (m == 0) return KNN_OK;
   if (k > 0 && (!d_idx || !d_dist || !d_lab))
     return knn_fail(KNN_ERR_ARG, "null neighbour rows / distances / labels");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   launch_wvote_sums(d_idx, d_dist, m, kmax, d_lab, idx_base, k, class_cnt, d_wsum,
-                    ctx->cu_count, s);
+                    ctx->cu_count, stream_of(ctx, stream));
   HIP_TRY(hipGetLastError());
   return KNN_OK;
 }
@@ -1893,9 +1782,8 @@ int knn_classify_sweep_eval_device(knn_ctx* ctx, const double* dQ, int64_t m,
                                    void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   return sweep_eval(ctx, dQ, m, d_excl, ks, nk, metric, d_labels, d_truth, d_correct, d_conf,
-                    d_unl, true, s);
+                    d_unl, stream_of(ctx, stream));
 }
 
 int knn_loo_sweep_eval_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks,
@@ -1903,9 +1791,8 @@ int knn_loo_sweep_eval_device(knn_ctx* ctx, int64_t row0, int64_t rows, const in
                               int64_t* d_conf, int64_t* d_unl, void* stream) {
   int rc;
   if ((rc = device_guard(ctx))) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  return knn_loo_eval_rows(ctx, row0, rows, ks, nk, metric, d_labels, d_correct, d_conf, d_unl,
-                           true, s);
+  return knn_sweep_rows(ctx, row0, rows, false, ks, nk, metric, d_labels, d_correct, nullptr,
+                        nullptr, nullptr, d_conf, d_unl, true, stream_of(ctx, stream));
 }
 
 int knn_classify_sweep_eval(knn_ctx* ctx, const double* Q, int64_t m, const int32_t* ks,
@@ -1918,41 +1805,8 @@ int knn_classify_sweep_eval(knn_ctx* ctx, const double* Q, int64_t m, const int3
   if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n, &kmax))) return rc;
   if (!truth) return knn_fail(KNN_ERR_ARG, "null truth (the evaluation needs the true labels)");
   if (m > 0 && !Q) return knn_fail(KNN_ERR_ARG, "null query pointer");
-  const int d = ctx->train.d;
-  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
-  const size_t m1 = (size_t)std::max<int64_t>(m, 1);
-  if ((rc = ctx->Q64.ensure(m1 * d * sizeof(double)))) return rc;
-  if ((rc = ctx->sw_truth.ensure(m1 * sizeof(int32_t)))) return rc;
-  if (out_labels && (rc = ctx->sw_out.ensure(m1 * nk * sizeof(int32_t)))) return rc;
-  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
-  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  hipStream_t s = ctx->stream;
-  if (m > 0) {
-    HIP_TRY(hipMemcpyAsync(ctx->Q64.p, Q, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->sw_truth.p, truth, (size_t)m * sizeof(int32_t),
-                           hipMemcpyHostToDevice, s));
-  }
-  rc = sweep_eval(ctx, (const double*)ctx->Q64.p, m, nullptr, ks, nk, metric,
-                  out_labels ? (int32_t*)ctx->sw_out.p : nullptr, (const int32_t*)ctx->sw_truth.p,
-                  out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
-                  out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
-                  out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, true, s);
-  if (rc) return rc;
-  if (out_labels && m > 0)
-    HIP_TRY(hipMemcpyAsync(out_labels, ctx->sw_out.p, (size_t)m * nk * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_correct)
-    HIP_TRY(hipMemcpyAsync(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_conf)
-    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_unl)
-    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return KNN_OK;
+  return host_sweep(ctx, Q, m, ks, nk, kmax, metric, true, out_labels, truth, out_correct,
+                    out_conf, out_unl, nullptr, nullptr, nullptr);
 }
 
 int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric,
@@ -1961,52 +1815,12 @@ int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metr
   int rc;
   if ((rc = device_guard(ctx))) return rc;
   if ((rc = check_query_args(ctx, 0, 0, metric))) return rc;
-  const int64_t n = ctx->train.n;
   int32_t kmax = 0;
-  if ((rc = knn_sweep_check_ks(ks, nk, n - 1, &kmax))) return rc;
-  // fixed batches: the workspace does not grow with n -- without out_labels no
-  // [nk][n] array exists anywhere
-  const int64_t B = std::min<int64_t>(n, 16384);
-  const int64_t nb = (n + B - 1) / B;
-  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
-  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
-  if (out_correct && (rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  if (out_conf && (rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
-  if (out_unl && (rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
-  hipStream_t s = ctx->stream;
-  // conf / unl are summed over the batches on the device, correct on the host
-  if (out_conf) HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
-  if (out_unl) HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
-  std::vector<int64_t> hc(out_correct ? (size_t)nb * nk : 0, 0);
-  for (int64_t b = 0; b < nb; b++) {
-    const int64_t r0 = b * B, rows = std::min(B, n - r0);
-    rc = knn_loo_eval_rows(ctx, r0, rows, ks, nk, metric, (int32_t*)ctx->sw_out.p,
-                  out_correct ? (int64_t*)ctx->sw_corr.p : nullptr,
-                  out_conf ? (int64_t*)ctx->ev_conf.p : nullptr,
-                  out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, false, s);
-    if (rc) return rc;
-    if (out_labels)
-      HIP_TRY(hipMemcpy2DAsync(out_labels + r0, (size_t)n * sizeof(int32_t), ctx->sw_out.p,
-                               (size_t)rows * sizeof(int32_t), (size_t)rows * sizeof(int32_t),
-                               (size_t)nk, hipMemcpyDeviceToHost, s));
-    if (out_correct)
-      HIP_TRY(hipMemcpyAsync(hc.data() + b * nk, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t),
-                             hipMemcpyDeviceToHost, s));
-  }
-  if (out_conf)
-    HIP_TRY(hipMemcpyAsync(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  if (out_unl)
-    HIP_TRY(hipMemcpyAsync(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (out_correct)
-    for (int32_t j = 0; j < nk; j++) {
-      out_correct[j] = 0;
-      for (int64_t b = 0; b < nb; b++) out_correct[j] += hc[(size_t)b * nk + j];
-    }
-  return KNN_OK;
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n - 1, &kmax))) return rc;
+  return host_rows_walk(ctx, false, ks, nk, kmax, metric, out_labels, out_correct, out_conf,
+                        out_unl, nullptr, nullptr, nullptr);
 }
+
 
 int knn_search_partial_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t w,
                               int32_t metric, double* d_dist, int64_t* d_idx, int32_t* d_lab,
@@ -2020,7 +1834,7 @@ int knn_search_partial_device(knn_ctx* ctx, const double* dQ, int64_t m, int32_t
   if (m < 0 || m >= (int64_t)INT32_MAX) return knn_fail(KNN_ERR_ARG, "bad m");
   if (!d_dist || !d_idx || !d_lab) return knn_fail(KNN_ERR_ARG, "null output");
   if (m == 0) return KNN_OK;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   Sink sink{};
   sink.mode = MODE_PARTIAL;
   sink.w = w;
@@ -2045,7 +1859,7 @@ int knn_merge_vote_device(knn_ctx* ctx, const double* d_dist, const int64_t* d_i
   if (q0 < 0 || mq < 0 || q0 + mq > m) return knn_fail(KNN_ERR_ARG, "query slice out of range");
   if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
   if (mq == 0) return KNN_OK;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   // unions beyond the LDS kernel's 4096 entries: rank merge through scratch
   if (const int64_t sb = merge_scratch_bytes(parts, w, k, mq))
     if ((rc = ctx->mrg.ensure((size_t)sb))) return rc;
@@ -2065,7 +1879,7 @@ int knn_shard_distances_device(knn_ctx* ctx, const double* dQ, const int32_t* d_
   if (nsel < 0 || metric < 0 || metric > 1) return knn_fail(KNN_ERR_ARG, "bad shard distance arguments");
   if (nsel == 0) return KNN_OK;
   if (!dQ || !d_out) return knn_fail(KNN_ERR_ARG, "null pointer");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   launch_shard_dist(metric, ctx->train, dQ, d_qsel, nsel, d_out, s);
   HIP_TRY(hipGetLastError());
   return KNN_OK;
@@ -2091,7 +1905,7 @@ int knn_tie_resolve_device(knn_ctx* ctx, const double* d_D, int32_t parts, const
   if (k <= 0 || k > n) return knn_fail(KNN_ERR_ARG, "k must be in [1, total rows]");
   if (nsel == 0) return KNN_OK;
   if (!d_D || !d_lab_all || !d_orow || !d_labels) return knn_fail(KNN_ERR_ARG, "null pointer");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   const int64_t per = tie_scratch_bytes(n, ctx->class_cnt);
   const int nwg = std::min<int>(tie_workgroups(ctx, per), nsel);
   if ((rc = ctx->tie_ws.ensure((size_t)(per * nwg)))) return rc;
@@ -2115,7 +1929,7 @@ int knn_minmax_device(knn_ctx* ctx, const double* d_X, int64_t rows, int32_t d, 
   if ((rc = device_guard(ctx))) return rc;
   if (rows < 0 || d <= 0 || (rows > 0 && !d_X) || !d_max || !d_min)
     return knn_fail(KNN_ERR_ARG, "bad minmax arguments");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   const int64_t R = minmax_rows_per_sweep(rows, d, ctx->cu_count);
   if ((rc = ctx->nrm_part.ensure((size_t)2 * d * R * sizeof(double)))) return rc;
   launch_minmax(d_X, rows, d, R, (double*)ctx->nrm_part.p, d_max, d_min, init, s);
@@ -2129,7 +1943,7 @@ int knn_normalize_device(knn_ctx* ctx, double* d_X, int64_t rows, int32_t d,
   if ((rc = device_guard(ctx))) return rc;
   if (rows < 0 || d <= 0 || (rows > 0 && !d_X) || !d_max || !d_min)
     return knn_fail(KNN_ERR_ARG, "bad normalize arguments");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   launch_normalize_apply(d_X, rows, d, minmax_rows_per_sweep(rows, d, ctx->cu_count), d_max,
                          d_min, s);
   HIP_TRY(hipGetLastError());
@@ -2376,7 +2190,7 @@ int knn_csv_parse_device(knn_ctx* ctx, const char* d_text, int64_t bytes, int32_
     return knn_fail(KNN_ERR_ARG, "bad slow list (slow_cap < 0, or null d_slow)");
   int64_t cap;
   if ((rc = csv_token_cap(dim, with_label != 0, rows, &cap))) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s = stream_of(ctx, stream);
   return csv_enqueue(ctx, d_text, bytes, dim, with_label != 0, cap, d_data, d_labels, d_tokens,
                      d_slow, slow_cap, d_nslow, false, s);
 }

@@ -154,18 +154,17 @@ int knn_fail(int code, const std::string& msg);
 // K sweep argument check shared with knn_group.cpp: 1 <= nk <= 4096 and 0 <=
 // ks[i] <= n (KNN_ERR_ARG naming the offending entry); *kmax = max K
 int knn_sweep_check_ks(const int32_t* ks, int32_t nk, int64_t n, int32_t* kmax);
-// Leave-one-out sweep with evaluation over train rows [row0, row0 + rows)
-// (knn_loo_sweep_eval_device's body): zero = false ADDS into d_conf / d_unl,
-// so the callers that walk the train set in batches sum them on the device
-int knn_loo_eval_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
-                      int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_conf,
-                      int64_t* d_unl, bool zero, hipStream_t s);
-// Leave-group-out sweep over train rows [row0, row0 + rows) with the optional
-// evaluation (knn_lgo_sweep_device's body; d_conf / d_unl nullable): zero =
-// false ADDS into d_conf / d_unl, as knn_loo_eval_rows
-int knn_lgo_rows(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t* ks, int32_t nk,
-                 int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
-                 double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl, bool zero,
-                 hipStream_t s);
+// K sweep of train rows [row0, row0 + rows) against the train set without the
+// row itself (own_group false: leave-one-out, the body of knn_loo_sweep_device
+// and knn_loo_sweep_eval_device) or without the row's whole group (own_group:
+// leave-group-out, knn_lgo_sweep_device's body), on stream s.  Every output is
+// nullable: without d_labels the labels stay in the context's workspace, d_conf
+// / d_unl ask for the per-class evaluation against the rows' own labels.  zero
+// = false ADDS into d_conf / d_unl, so the callers that walk the train set in
+// batches sum them on the device.
+int knn_sweep_rows(knn_ctx* ctx, int64_t row0, int64_t rows, bool own_group, const int32_t* ks,
+                   int32_t nk, int32_t metric, int32_t* d_labels, int64_t* d_correct,
+                   int64_t* d_idx, double* d_dist, int32_t* d_flags, int64_t* d_conf,
+                   int64_t* d_unl, bool zero, hipStream_t s);
 int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                    const knnk::Sink& sink, hipStream_t s);

@@ -1071,19 +1071,10 @@ static int group_loo(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric
     }
     for (int64_t b = 0; b < nb; b++) {
       const int64_t q0 = r0 + b * B, rows = std::min(B, r1 - q0);
-      if (lgo)
-        rc = knn_lgo_rows(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
+      rc = knn_sweep_rows(g->ctx[i], q0, rows, lgo, ks, nk, metric, (int32_t*)g->slab[i].p,
                           out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr, nullptr,
                           nullptr, eval ? (int64_t*)g->sconf[i].p : nullptr,
                           eval ? (int64_t*)g->sunl[i].p : nullptr, false, s);
-      else if (eval)
-        rc = knn_loo_eval_rows(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
-                               out_correct ? (int64_t*)g->scorr[i].p : nullptr,
-                               (int64_t*)g->sconf[i].p, (int64_t*)g->sunl[i].p, false, s);
-      else
-        rc = knn_loo_sweep_device(g->ctx[i], q0, rows, ks, nk, metric, (int32_t*)g->slab[i].p,
-                                  out_correct ? (int64_t*)g->scorr[i].p : nullptr, nullptr,
-                                  nullptr, nullptr, s);
       if (rc) return rc;
       if (out_labels)
         HIP_G(hipMemcpy2DAsync(out_labels + q0, (size_t)n * sizeof(int32_t), g->slab[i].p,
