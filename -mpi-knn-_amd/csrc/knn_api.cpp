@@ -88,6 +88,18 @@ static int copy_back(void* dst, const void* src, size_t bytes, hipStream_t s) {
   return KNN_OK;
 }
 
+// Drops the folds of knn_set_folds: the sub-contexts and the fold-major copy
+// (they belong to one train set, like the group ids).
+static void fold_clear(knn_ctx* ctx) {
+  for (knn_ctx* sub : ctx->fold_ctx) knn_destroy(sub);
+  ctx->fold_ctx.clear();
+  ctx->fold_off.clear();
+  ctx->fold_rows.clear();
+  ctx->n_folds = ctx->fold_max = 0;
+  ctx->fold_X.release();
+  ctx->fold_lab.release();
+}
+
 extern "C" {
 
 const char* knn_version(void) { return "mpi-knn-amd 0.1 (gfx950)"; }
@@ -143,6 +155,7 @@ int knn_destroy(knn_ctx* ctx) {
   if (!ctx) return KNN_OK;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  fold_clear(ctx);
   for (DevBuf* b : ctx->all_bufs()) b->release();
   for (auto& tc : ctx->ring)
     for (auto& e : tc.ev)
@@ -268,6 +281,10 @@ static int build_train(knn_ctx* ctx, const double* dX, const int32_t* dlab, int6
   int rc;
   ctx->groups = nullptr;  // group ids belong to one train set (knn_set_groups)
   ctx->n_groups = ctx->gmax = 0;
+  if (ctx->n_folds) {  // and so do the folds (knn_set_folds); their work may still run
+    HIP_TRY(hipDeviceSynchronize());
+    fold_clear(ctx);
+  }
   // padded rows [payload | seeds] (+1 KiB slack: the last LDS-DMA piece of
   // the last tile may read past the final row)
   if ((rc = ctx->X32.ensure((size_t)n_pad * (DP + 4) * sizeof(float) + 1024))) return rc;
@@ -1416,6 +1433,177 @@ static int host_rows_walk(knn_ctx* ctx, bool own_group, const int32_t* ks, int32
   return KNN_OK;
 }
 
+// ---- F-fold cross-validated K sweep on fold shards (knn_fold.hip)
+
+constexpr int64_t kFoldBatch = 16384;  // queries per batch, as the leave-one-out walk
+
+// knn_kfold_sweep* up to the first launch: the state, the list of K against
+// the rows the smallest remaining set holds, the metric
+static int fold_check(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* kmax) {
+  int rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "k-fold sweep before set_train");
+  if (!ctx->n_folds) return knn_fail(KNN_ERR_STATE, "k-fold sweep before knn_set_folds");
+  if (metric != KNN_METRIC_L2 && metric != KNN_METRIC_L1)
+    return knn_fail(KNN_ERR_ARG, "metric must be 0 (L2) or 1 (L1)");
+  if ((rc = knn_sweep_check_ks(ks, nk, ctx->train.n - ctx->fold_max, kmax))) return rc;
+  return KNN_OK;
+}
+
+// Rows [j0, j0 + m) of fold f (positions in the fold's ascending row order, m
+// <= kFoldBatch) against the other F - 1 shards, on stream s; the list of K is
+// on the device already (sw_ks).  L [nk][m] and idx / dist [m][kmax], flags
+// [m] are device buffers of the batch (all required); d_correct / d_conf /
+// d_unl (nullable) are ADDED into.  Enqueue only.
+static int fold_batch(knn_ctx* ctx, int f, int64_t j0, int64_t m, int32_t nk, int32_t kmax,
+                      int32_t metric, int32_t* L, int64_t* d_correct, int64_t* d_idx,
+                      double* d_dist, int32_t* d_flags, int64_t* d_conf, int64_t* d_unl,
+                      hipStream_t s) {
+  int rc;
+  const TrainDev& t = ctx->train;
+  const int F = ctx->n_folds, parts = F - 1;
+  const int64_t first = ctx->fold_off[f] + j0;
+  const double* dQ = (const double*)ctx->fold_X.p + first * t.d;  // the queries: no staging copy
+  const int32_t* truth = (const int32_t*)ctx->fold_lab.p + first;
+  const int32_t* vtruth = d_correct ? truth : nullptr;  // (the votes count only into d_correct)
+  const int* dks = (const int*)ctx->sw_ks.p;
+  if (kmax == 0) {  // every K is 0: no neighbour is read, every label is -1
+    launch_sweep_vote(nullptr, m, 0, t.lab, ctx->idx_off, dks, nk, L, vtruth,
+                      (unsigned long long*)d_correct, ctx->cu_count, s);
+    launch_fill_i32(d_flags, m, 0, s);
+  } else {
+    // each shard's exact top w, sorted by (dist, local row), into the packed
+    // [parts][m][w] layout; shards below w rows arrive padded (idx -1, dist +inf)
+    const int64_t n_rest = t.n - (ctx->fold_off[f + 1] - ctx->fold_off[f]);
+    const int w = (int)std::min<int64_t>((int64_t)kmax + 1, n_rest);
+    const int64_t PB = packed_part_bytes(m, w);
+    if ((rc = ctx->fold_pk.ensure((size_t)(parts * PB)))) return rc;
+    if ((rc = ctx->sw_lab.ensure((size_t)m * sizeof(int32_t)))) return rc;
+    if (const int64_t sb = merge_scratch_bytes(parts, w, kmax, m))
+      if ((rc = ctx->mrg.ensure((size_t)sb))) return rc;
+    int p = 0;
+    for (int g = 0; g < F; g++) {
+      if (g == f) continue;
+      knn_ctx* sub = ctx->fold_ctx[g];
+      sub->precision = ctx->precision;  // the parent's choices reach every shard
+      sub->tune = ctx->tune;
+      unsigned char* pb = (unsigned char*)ctx->fold_pk.p + (int64_t)p * PB;
+      int64_t* pidx = (int64_t*)(pb + 8 * m * w);
+      if ((rc = knn_search_partial_device(sub, dQ, m, w, metric, (double*)pb, pidx,
+                                          (int32_t*)(pb + 16 * m * w), s)))
+        return rc;
+      // local rows -> original rows; rows_of[g] ascends, so the list stays
+      // sorted by (dist, idx) and the merge breaks cross-shard ties by train row
+      launch_fold_map_idx(pidx, m * w, (const int32_t*)ctx->fold_rowsd.p + ctx->fold_off[g],
+                          ctx->fold_off[g + 1] - ctx->fold_off[g], ctx->idx_off, ctx->cu_count, s);
+      ctx->last_kmetric = sub->last_kmetric;  // (the last shard search is the call's)
+      memcpy(ctx->last_kernel, sub->last_kernel, sizeof ctx->last_kernel);
+      p++;
+    }
+    launch_merge_vote_partials((const double*)ctx->fold_pk.p, nullptr, nullptr, parts, m, w, kmax,
+                               (int32_t*)ctx->sw_lab.p, d_idx, d_dist, d_flags, s, 0, m, PB,
+                               ctx->mrg.p, MergeTies{});
+    // the queries whose label at some K the reference's order among equal
+    // distances could change: its std::sort over the n - n_f remaining records
+    // in row order is the leave-group-out pass with the fold as the group
+    if (ctx->tune.ties) {
+      const int64_t per = tie_scratch_bytes(t.n, ctx->class_cnt);
+      const int nwg = tie_workgroups(ctx, per);
+      if ((rc = ctx->fold_tq.ensure((size_t)m * sizeof(int) + 16))) return rc;
+      if ((rc = ctx->fold_qg.ensure((size_t)m * sizeof(int32_t)))) return rc;
+      if ((rc = ctx->tie_ws.ensure((size_t)(per * nwg)))) return rc;
+      int* tq = (int*)ctx->fold_tq.p + 4;
+      int* tcnt = (int*)ctx->fold_tq.p;
+      HIP_TRY(hipMemsetAsync(tcnt, 0, sizeof(int), s));
+      launch_fill_i32((int32_t*)ctx->fold_qg.p, m, f, s);
+      launch_sweep_tie_scan(d_dist, d_idx, d_flags, m, kmax, t.lab, ctx->idx_off, dks, nk,
+                            ctx->tune.ties, tq, tcnt, ctx->cu_count, s);
+      Sink out{};
+      out.mode = MODE_SINGLE;
+      out.k = kmax;
+      out.idx_off = ctx->idx_off;
+      out.labels = (int32_t*)ctx->sw_lab.p;
+      out.idx = d_idx;
+      out.dist = d_dist;
+      out.flags = d_flags;
+      out.tie_mode = ctx->tune.ties;
+      launch_tie_order_group(metric, t, dQ, tq, tcnt, ctx->class_cnt,
+                             (unsigned char*)ctx->tie_ws.p, per, nwg, out,
+                             (unsigned long long*)ctx->totals.p + 2, s,
+                             (const int32_t*)ctx->fold_qg.p, (const int32_t*)ctx->fold_ids.p);
+    }
+    sweep_votes(ctx, d_idx, d_dist, m, kmax, dks, nk, L, vtruth, d_correct, s);
+  }
+  if (d_conf || d_unl)
+    launch_eval_confusion(L, nk, m, truth, ctx->class_cnt, (unsigned long long*)d_conf,
+                          (unsigned long long*)d_unl, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->done_ev, s));
+  ctx->auto_pending = false;  // done_ev now belongs to this call
+  return KNN_OK;
+}
+
+int knn_kfold_walk(knn_ctx* ctx, int fold0, int step, const int32_t* ks, int32_t nk,
+                   int32_t metric, int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                   int64_t* out_unl, int64_t* out_idx, double* out_dist, int32_t* out_flags) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  int32_t kmax = 0;
+  if ((rc = fold_check(ctx, ks, nk, metric, &kmax))) return rc;
+  if (fold0 < 0 || step < 1) return knn_fail(KNN_ERR_ARG, "bad fold walk");
+  const int64_t n = ctx->train.n;
+  const int64_t B = std::min<int64_t>(ctx->fold_max, kFoldBatch);
+  const size_t bk = (size_t)B * std::max(kmax, 1);
+  const size_t cc = (size_t)ctx->class_cnt * ctx->class_cnt;
+  if ((rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->sw_corr.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->ev_conf.ensure((size_t)nk * cc * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->ev_unl.ensure((size_t)nk * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
+  if ((rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
+  if ((rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
+  hipStream_t s = ctx->stream;
+  if ((rc = sweep_upload(ctx, ks, nk, (int64_t*)ctx->sw_corr.p, s))) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->ev_conf.p, 0, (size_t)nk * cc * sizeof(int64_t), s));
+  HIP_TRY(hipMemsetAsync(ctx->ev_unl.p, 0, (size_t)nk * sizeof(int64_t), s));
+  // a batch's rows come back in the fold's order and are placed by rows_of
+  std::vector<int32_t> hl(out_labels ? (size_t)B * nk : 0), hf(out_flags ? (size_t)B : 0);
+  std::vector<int64_t> hi(out_idx ? bk : 0);
+  std::vector<double> hd(out_dist ? bk : 0);
+  for (int f = fold0; f < ctx->n_folds; f += step) {
+    const int64_t nf = ctx->fold_off[f + 1] - ctx->fold_off[f];
+    for (int64_t j0 = 0; j0 < nf; j0 += B) {
+      const int64_t m = std::min(B, nf - j0);
+      rc = fold_batch(ctx, f, j0, m, nk, kmax, metric, (int32_t*)ctx->sw_out.p,
+                      out_correct ? (int64_t*)ctx->sw_corr.p : nullptr, (int64_t*)ctx->o_idx.p,
+                      (double*)ctx->o_dist.p, (int32_t*)ctx->o_flags.p,
+                      out_conf || out_unl ? (int64_t*)ctx->ev_conf.p : nullptr,
+                      out_conf || out_unl ? (int64_t*)ctx->ev_unl.p : nullptr, s);
+      if (rc) return rc;
+      if (!out_labels && !out_flags && !out_idx && !out_dist) continue;
+      const size_t mk = (size_t)m * kmax;
+      if ((rc = copy_back(hl.data(), ctx->sw_out.p, out_labels ? (size_t)m * nk * 4 : 0, s))) return rc;
+      if ((rc = copy_back(hf.data(), ctx->o_flags.p, out_flags ? (size_t)m * 4 : 0, s))) return rc;
+      if ((rc = copy_back(hi.data(), ctx->o_idx.p, out_idx ? mk * 8 : 0, s))) return rc;
+      if ((rc = copy_back(hd.data(), ctx->o_dist.p, out_dist ? mk * 8 : 0, s))) return rc;
+      HIP_TRY(hipStreamSynchronize(s));
+      const int32_t* rows = ctx->fold_rows.data() + ctx->fold_off[f] + j0;
+      for (int64_t q = 0; q < m; q++) {
+        const int64_t r = rows[q];
+        if (out_labels)
+          for (int32_t j = 0; j < nk; j++) out_labels[(size_t)j * n + r] = hl[(size_t)j * m + q];
+        if (out_flags) out_flags[r] = hf[q];
+        if (out_idx && kmax) memcpy(out_idx + r * kmax, hi.data() + q * kmax, (size_t)kmax * 8);
+        if (out_dist && kmax) memcpy(out_dist + r * kmax, hd.data() + q * kmax, (size_t)kmax * 8);
+      }
+    }
+  }
+  if ((rc = copy_back(out_correct, ctx->sw_corr.p, (size_t)nk * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_conf, ctx->ev_conf.p, (size_t)nk * cc * sizeof(int64_t), s))) return rc;
+  if ((rc = copy_back(out_unl, ctx->ev_unl.p, (size_t)nk * sizeof(int64_t), s))) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  return KNN_OK;
+}
+
 // ---- votes over caller-supplied rows (knn_sweep.hip, knn_eval.hip, knn_wvote.hip)
 
 // knn_vote_sweep_device / knn_vote_sweep_weighted_device up to the launch:
@@ -1700,6 +1888,139 @@ int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, i
   if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
   return host_rows_walk(ctx, true, ks, nk, kmax, metric, out_labels, out_correct, out_conf,
                         out_unl, out_idx, out_dist, out_flags);
+}
+
+
+// ---- F-fold cross-validated K sweep on fold shards (knn_fold.hip)
+
+int knn_set_folds(knn_ctx* ctx, const int32_t* folds, int32_t n_folds) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  if (!ctx->trained) return knn_fail(KNN_ERR_STATE, "set_folds before set_train");
+  if (ctx->n_folds) {  // (work of the last folds may still run on a caller's stream)
+    HIP_TRY(hipDeviceSynchronize());
+    fold_clear(ctx);
+  }
+  if (!folds) return KNN_OK;  // clears the folds
+  if (n_folds < 2 || n_folds > kMaxParts)
+    return knn_fail(KNN_ERR_ARG, "n_folds = " + std::to_string(n_folds) + " must be in [2, 64]");
+  const TrainDev& t = ctx->train;
+  const int64_t n = t.n;
+  const int d = t.d;
+  // the range check and the fold sizes: set_groups' kernel
+  if ((rc = ctx->fold_ids.ensure((size_t)n * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->grp_hist.ensure((size_t)n_folds * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->grp_stat.ensure(2 * sizeof(unsigned long long)))) return rc;
+  hipStream_t s = ctx->stream;
+  unsigned long long h[2] = {(unsigned long long)n, 0};  // first bad row (n: none) | largest fold
+  std::vector<int32_t> hist((size_t)n_folds, 0);
+  HIP_TRY(hipMemcpyAsync(ctx->fold_ids.p, folds, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(ctx->grp_hist.p, 0, (size_t)n_folds * sizeof(int32_t), s));
+  HIP_TRY(hipMemcpyAsync(ctx->grp_stat.p, h, sizeof(h), hipMemcpyHostToDevice, s));
+  launch_lgo_group_stats((const int32_t*)ctx->fold_ids.p, n, n_folds, (int32_t*)ctx->grp_hist.p,
+                         (unsigned long long*)ctx->grp_stat.p,
+                         (int32_t*)((unsigned long long*)ctx->grp_stat.p + 1), ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, ctx->grp_stat.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(hist.data(), ctx->grp_hist.p, (size_t)n_folds * sizeof(int32_t),
+                         hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h[0] < (unsigned long long)n)
+    return knn_fail(KNN_ERR_ARG, "fold id out of [0, n_folds) at row " + std::to_string(h[0]));
+  for (int f = 0; f < n_folds; f++)
+    if (hist[f] <= 0) return knn_fail(KNN_ERR_ARG, "fold " + std::to_string(f) + " is empty");
+  // rows_of: the stable fold-major order (inside a fold the rows ascend)
+  std::vector<int64_t> off((size_t)n_folds + 1, 0);
+  for (int f = 0; f < n_folds; f++) off[f + 1] = off[f] + hist[f];
+  std::vector<int32_t> rows((size_t)n);
+  {
+    std::vector<int64_t> at(off.begin(), off.end() - 1);
+    for (int64_t r = 0; r < n; r++) rows[(size_t)at[folds[r]]++] = (int32_t)r;
+  }
+  if ((rc = ctx->fold_rowsd.ensure((size_t)n * sizeof(int32_t)))) return rc;
+  if ((rc = ctx->fold_X.ensure((size_t)n * d * sizeof(double)))) return rc;
+  if ((rc = ctx->fold_lab.ensure((size_t)n * sizeof(int32_t)))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->fold_rowsd.p, rows.data(), (size_t)n * sizeof(int32_t),
+                         hipMemcpyHostToDevice, s));
+  launch_fold_gather(t.X64, t.lab, (const int32_t*)ctx->fold_rowsd.p, n, d, (double*)ctx->fold_X.p,
+                     (int32_t*)ctx->fold_lab.p, ctx->cu_count, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  // one sub-context per fold over its (borrowed) slice, local indices from 0;
+  // precision and tuning are the parent's, the vote stays with the parent
+  for (int f = 0; f < n_folds; f++) {
+    knn_ctx* sub = nullptr;
+    if ((rc = knn_create(&sub, ctx->device))) break;
+    ctx->fold_ctx.push_back(sub);
+    sub->precision = ctx->precision;
+    sub->tune = ctx->tune;
+    if ((rc = knn_set_train_device(sub, (const double*)ctx->fold_X.p + off[f] * d,
+                                   (const int32_t*)ctx->fold_lab.p + off[f], hist[f], d,
+                                   ctx->class_cnt, 0)))
+      break;
+  }
+  if (rc) {
+    const std::string msg = knn_last_error();
+    fold_clear(ctx);
+    return knn_fail(rc, "fold shard: " + msg);
+  }
+  ctx->fold_off = std::move(off);
+  ctx->fold_rows = std::move(rows);
+  ctx->n_folds = n_folds;
+  ctx->fold_max = (int32_t)(h[1] & 0xffffffffu);
+  return KNN_OK;
+}
+
+int32_t knn_get_fold_max(knn_ctx* ctx) { return ctx ? ctx->fold_max : 0; }
+
+int knn_kfold_sweep_device(knn_ctx* ctx, int32_t fold, const int32_t* ks, int32_t nk,
+                           int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                           double* d_dist, int32_t* d_flags, void* on_stream) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  int32_t kmax = 0;
+  if ((rc = fold_check(ctx, ks, nk, metric, &kmax))) return rc;
+  if (fold < 0 || fold >= ctx->n_folds)
+    return knn_fail(KNN_ERR_ARG, "fold = " + std::to_string(fold) + " outside [0, " +
+                                     std::to_string(ctx->n_folds) + ")");
+  if (!d_labels) return knn_fail(KNN_ERR_ARG, "null labels output");
+  hipStream_t s = stream_of(ctx, on_stream);
+  const int64_t nf = ctx->fold_off[fold + 1] - ctx->fold_off[fold];
+  const int64_t B = std::min<int64_t>(nf, kFoldBatch);
+  const size_t bk = (size_t)B * std::max(kmax, 1);
+  if (nf > B && (rc = ctx->sw_out.ensure((size_t)B * nk * sizeof(int32_t)))) return rc;
+  if (!d_idx && (rc = ctx->o_idx.ensure(bk * sizeof(int64_t)))) return rc;
+  if (!d_dist && (rc = ctx->o_dist.ensure(bk * sizeof(double)))) return rc;
+  if (!d_flags && (rc = ctx->o_flags.ensure((size_t)B * sizeof(int32_t)))) return rc;
+  if ((rc = sweep_upload(ctx, ks, nk, d_correct, s))) return rc;
+  for (int64_t j0 = 0; j0 < nf; j0 += B) {
+    const int64_t m = std::min(B, nf - j0);
+    // one batch writes the caller's [nk][nf] rows itself; several go through
+    // the workspace, each into its columns
+    int32_t* L = nf > B ? (int32_t*)ctx->sw_out.p : d_labels;
+    rc = fold_batch(ctx, fold, j0, m, nk, kmax, metric, L, d_correct,
+                    d_idx ? d_idx + j0 * kmax : (int64_t*)ctx->o_idx.p,
+                    d_dist ? d_dist + j0 * kmax : (double*)ctx->o_dist.p,
+                    d_flags ? d_flags + j0 : (int32_t*)ctx->o_flags.p, nullptr, nullptr, s);
+    if (rc) return rc;
+    if (nf > B)
+      HIP_TRY(hipMemcpy2DAsync(d_labels + j0, (size_t)nf * sizeof(int32_t), L,
+                               (size_t)m * sizeof(int32_t), (size_t)m * sizeof(int32_t),
+                               (size_t)nk, hipMemcpyDeviceToDevice, s));
+  }
+  return KNN_OK;
+}
+
+int knn_kfold_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric,
+                    int32_t* out_labels, int64_t* out_correct, int64_t* out_conf, int64_t* out_unl,
+                    int64_t* out_idx, double* out_dist, int32_t* out_flags) {
+  int rc;
+  if ((rc = device_guard(ctx))) return rc;
+  int32_t kmax = 0;
+  if ((rc = fold_check(ctx, ks, nk, metric, &kmax))) return rc;
+  if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
+  return knn_kfold_walk(ctx, 0, 1, ks, nk, metric, out_labels, out_correct, out_conf, out_unl,
+                        out_idx, out_dist, out_flags);
 }
 
 

@@ -121,6 +121,17 @@ struct knn_ctx {
   const int32_t* groups = nullptr;
   int32_t n_groups = 0, gmax = 0;
   DevBuf grp_own, grp_hist, grp_stat, lgo_qg;
+  // K-fold sweep on fold shards (knn_set_folds): the fold count and the largest
+  // fold's size (0 = none set), the folds' first rows in the fold-major order
+  // [n_folds + 1], that order's original train rows (rows_of, host copy), one
+  // sub-context per fold over its slice of the fold-major fp64 copy; on the
+  // device: the fold ids, rows_of, the copy and its labels, the packed partial
+  // lists [F - 1][m][w] of a batch, its queries' fold, its tie queue | count
+  int32_t n_folds = 0, fold_max = 0;
+  std::vector<int64_t> fold_off;
+  std::vector<int32_t> fold_rows;
+  std::vector<knn_ctx*> fold_ctx;
+  DevBuf fold_ids, fold_rowsd, fold_X, fold_lab, fold_pk, fold_qg, fold_tq;
   // per-class evaluation: the sweep's labels [nk][m] when the caller wants
   // none, host-API staging of conf [nk][C][C] and unl [nk]
   DevBuf ev_lab, ev_conf, ev_unl;
@@ -145,6 +156,7 @@ struct knn_ctx {
             &ord_qkey, &ord_qperm, &ord_qpos, &ord_qstart, &ord_perm0, &sw_ks, &sw_lab, &sw_idx, &sw_dist, &sw_flags,
             &sw_out, &sw_truth, &sw_corr, &loo_idx, &loo_dist, &loo_flags, &loo_excl,
             &grp_own, &grp_hist, &grp_stat, &lgo_qg,
+            &fold_ids, &fold_rowsd, &fold_X, &fold_lab, &fold_pk, &fold_qg, &fold_tq,
             &ev_lab, &ev_conf, &ev_unl, &csv_tab, &csv_ws, &csv_text, &csv_data, &csv_lab, &csv_slow,
             &csv_misc, &csv_fix};
   }
@@ -166,5 +178,13 @@ int knn_sweep_rows(knn_ctx* ctx, int64_t row0, int64_t rows, bool own_group, con
                    int32_t nk, int32_t metric, int32_t* d_labels, int64_t* d_correct,
                    int64_t* d_idx, double* d_dist, int32_t* d_flags, int64_t* d_conf,
                    int64_t* d_unl, bool zero, hipStream_t s);
+// K-fold sweep (knn_kfold_sweep's body, shared with knn_group.cpp): folds fold0,
+// fold0 + step, ... of the context's folds, each in batches of at most 16384 of
+// its rows; the outputs are host arrays in train row order of which only the
+// walked folds' rows are written, out_correct / out_conf / out_unl receive the
+// walk's own sums.  Every output is nullable; waits for the result.
+int knn_kfold_walk(knn_ctx* ctx, int fold0, int step, const int32_t* ks, int32_t nk,
+                   int32_t metric, int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                   int64_t* out_unl, int64_t* out_idx, double* out_dist, int32_t* out_flags);
 int knn_run_search(knn_ctx* ctx, const double* dQ, int64_t m, int W, int metric,
                    const knnk::Sink& sink, hipStream_t s);

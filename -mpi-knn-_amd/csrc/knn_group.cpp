@@ -1150,6 +1150,56 @@ int knn_group_lgo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t met
                    out_conf || out_unl, true);
 }
 
+int knn_group_set_folds(knn_group* g, const int32_t* folds, int32_t n_folds) {
+  if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group set_folds before set_train");
+  if (g->mode == 1)
+    return knn_fail(KNN_ERR_ARG,
+                    "folds are not served in the train-sharded mode (mode 1): "
+                    "use a query-sharded group (mode 0)");
+  // every rank holds the whole train set and builds its own fold shards
+  return for_each_dev(g, [&](int i) { return knn_set_folds(g->ctx[i], folds, n_folds); });
+}
+
+// K-fold sweep (knn_fold.hip): rank r walks folds r, r + G, ... of its own
+// shards in a host thread of its own; the ranks' rows are disjoint columns of
+// out_labels, their counts are summed here.
+int knn_group_kfold_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                          int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                          int64_t* out_unl) {
+  if (!g || !g->trained) return knn_fail(KNN_ERR_STATE, "group k-fold sweep before set_train");
+  if (g->mode == 1)
+    return knn_fail(KNN_ERR_ARG,
+                    "the leave-one-out sweep is not served in the train-sharded mode (mode 1): "
+                    "use a query-sharded group (mode 0)");
+  if (!knn_get_fold_max(g->ctx[0]))
+    return knn_fail(KNN_ERR_STATE, "group k-fold sweep before set_folds");
+  if (!out_labels && !out_conf) return knn_fail(KNN_ERR_ARG, "null labels output");
+  int rc;
+  int32_t kmax = 0;
+  if ((rc = knn_sweep_check_ks(ks, nk, g->n - knn_get_fold_max(g->ctx[0]), &kmax))) return rc;
+  const int G = g->ndev;
+  const size_t cc = (size_t)g->class_cnt * g->class_cnt;
+  std::vector<std::vector<int64_t>> hc(G, std::vector<int64_t>((size_t)nk, 0)),
+      hconf(G, std::vector<int64_t>((size_t)nk * cc, 0)), hunl(G, std::vector<int64_t>((size_t)nk, 0));
+  rc = for_each_dev(g, [&](int i) {
+    return knn_kfold_walk(g->ctx[i], i, G, ks, nk, metric, out_labels,
+                          out_correct ? hc[i].data() : nullptr,
+                          out_conf ? hconf[i].data() : nullptr, out_unl ? hunl[i].data() : nullptr,
+                          nullptr, nullptr, nullptr);
+  });
+  if (rc) return rc;
+  g->last_ties = 0;
+  if (out_correct) std::fill(out_correct, out_correct + nk, (int64_t)0);
+  if (out_conf) std::fill(out_conf, out_conf + (size_t)nk * cc, (int64_t)0);
+  if (out_unl) std::fill(out_unl, out_unl + nk, (int64_t)0);
+  for (int i = 0; i < G; i++) {
+    for (int32_t j = 0; out_correct && j < nk; j++) out_correct[j] += hc[i][j];
+    for (size_t j = 0; out_conf && j < (size_t)nk * cc; j++) out_conf[j] += hconf[i][j];
+    for (int32_t j = 0; out_unl && j < nk; j++) out_unl[j] += hunl[i][j];
+  }
+  return KNN_OK;
+}
+
 double knn_group_last_compute_seconds(knn_group* g) { return g ? g->last_compute : -1.0; }
 
 int64_t knn_group_last_tie_count(knn_group* g) { return g ? g->last_ties : -1; }

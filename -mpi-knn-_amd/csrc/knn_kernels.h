@@ -437,6 +437,15 @@ void launch_lgo_self(int32_t* qgroup, const int32_t* groups, int64_t rows, int64
 // largest group's size into *gmax (zeroed by the caller)
 void launch_lgo_group_stats(const int32_t* groups, int64_t n, int32_t n_groups, int32_t* hist,
                             unsigned long long* bad, int32_t* gmax, int cus, hipStream_t s);
+// K-fold sweep on fold shards (knn_fold.hip).  rows [n]: the original train
+// row of every row of the fold-major order (ascending inside a fold); the
+// gather writes Xf [n][d] and labf [n] in that order
+void launch_fold_gather(const double* X, const int32_t* lab, const int32_t* rows, int64_t n, int d,
+                        double* Xf, int32_t* labf, int cus, hipStream_t s);
+// a shard's list indices (local rows of fold g, -1 = padded slot) rewritten in
+// place to base + rows_g[local]: original train rows, the lists still sorted
+void launch_fold_map_idx(int64_t* idx, int64_t cnt, const int32_t* rows_g, int64_t n_g,
+                         int64_t base, int cus, hipStream_t s);
 // K sweep under exclusion (knn_loo.hip): compacts the search's rows at kmax + 1
 // (in_dist / in_idx [m][kmax + 1], in_flags [m]) into [m][kmax] rows without
 // train row excl[q] (global index; excl null or a value outside [idx_base,

@@ -34,6 +34,12 @@
 // against the rows of all the other groups -- samples of one subject, copies
 // of one image), prints "K = <k> lgo accuracy = <acc>" per K and selects K the
 // same way.  Without the flag stdout is unchanged.
+// --kfold F (needs --K_list, 2 <= F <= 64, not with --loo; no validation file
+// is read): F-fold cross-validation on fold shards (knn_group_set_folds,
+// knn_group_kfold_sweep: every train row judged against the rows of the other
+// folds), prints "K = <k> kfold accuracy = <acc>" per K and selects K the same
+// way.  --folds FILE holds one fold id in [0, F) per train row (read like
+// --groups); without it row r is in fold r % F.
 // --confusion (with the default validation pass, --K_list or --loo): after that
 // pass's lines prints "confusion K = <k>" for the selected K, then class_cnt
 // lines of class_cnt space-separated counts (row = true class, column =
@@ -89,6 +95,8 @@ struct Config {
   std::vector<int32_t> K_list;  // --K_list (empty: the single --K)
   bool loo = false;             // --loo: judge the K of --K_list by leave-one-out on the train set
   std::string groups_file;      // --groups: with --loo, leave out the row's whole group
+  int kfold = 0;                // --kfold F: judge the K of --K_list by F-fold cross-validation
+  std::string folds_file;       // --folds: one fold id per train row (default: row % F)
   bool confusion = false;       // --confusion: print the selected K's confusion matrix
   int vote = KNN_VOTE_UNIFORM;  // --weights uniform|distance
   bool csv_gpu = false;         // --csv gpu: the files are parsed on device 0
@@ -104,7 +112,7 @@ void usage() {
           "  [--Validation true|false] [--train_file F] [--validation_file F]\n"
           "  [--test_file F] [--output F] [--gpus G] [--mode query|train] [--strict]\n"
           "  [--threads T] [--timings] [--K_list K1,K2,...] [--loo] [--confusion]\n"
-          "  [--groups F]\n"
+          "  [--groups F] [--kfold F] [--folds FILE]\n"
           "  [--tune KEY=VALUE]... [--weights uniform|distance] [--csv host|gpu]\n"
           "  --K_list needs --Validation true: one search scores every K on the validation\n"
           "  set; the test pass runs at the first K with the best accuracy\n"
@@ -112,6 +120,10 @@ void usage() {
           "  (no validation file is read)\n"
           "  --groups F needs --loo --K_list: F holds one integer group id per train row;\n"
           "  every row is judged without the rows of its own group (leave-one-group-out)\n"
+          "  --kfold F needs --K_list: scores every K by F-fold cross-validation on the train\n"
+          "  set (2 <= F <= 64; every row judged without the rows of its own fold; no\n"
+          "  validation file is read; not together with --loo); --folds FILE holds one fold\n"
+          "  id in [0, F) per train row, without it row r is in fold r mod F\n"
           "  --confusion prints the confusion matrix of the validation (or --loo) pass at the\n"
           "  selected K: class_cnt rows (true class) of class_cnt counts (predicted class)\n"
           "  --weights distance: every pass votes with weight 1 / distance (exact matches\n"
@@ -171,6 +183,8 @@ int parse_args(int argc, char** argv, Config& c) {
     else if (a == "test_file") c.test_file = v;
     else if (a == "output") c.output = v;
     else if (a == "groups") c.groups_file = v;
+    else if (a == "kfold") c.kfold = atoi(v.c_str());
+    else if (a == "folds") c.folds_file = v;
     else if (a == "gpus") c.gpus = atoi(v.c_str());
     else if (a == "mode") c.mode = (v == "train" || v == "1") ? 1 : 0;
     else if (a == "strict") c.strict = parse_bool(v);
@@ -274,13 +288,17 @@ int main(int argc, char** argv) {
   if (c.loo && c.K_list.empty()) die("--loo needs --K_list (the K to judge by leave-one-out)");
   if (!c.groups_file.empty() && (!c.loo || c.K_list.empty()))
     die("--groups needs --loo --K_list (the groups are left out of the leave-one-out sweep)");
-  if (c.loo) c.Validation = false;  // the train set is its own validation set: no file is read
+  if (c.kfold && c.loo) die("--kfold and --loo exclude each other (one way to judge K)");
+  if (c.kfold && (c.kfold < 2 || c.kfold > 64)) die("--kfold takes a fold count in [2, 64]");
+  if (c.kfold && c.K_list.empty()) die("--kfold needs --K_list (the K to judge by cross-validation)");
+  if (!c.folds_file.empty() && !c.kfold) die("--folds needs --kfold F --K_list");
+  if (c.loo || c.kfold) c.Validation = false;  // the train set is its own validation set: no file is read
   if (c.strict && (c.N_train % c.gpus || c.N_test % c.gpus || (c.Validation && c.N_val % c.gpus)))
     die("N_train/N_test/N_val not divisible by the number of GPUs (--strict, cpp:127-129)");
   if (!c.K_list.empty()) {
-    if (!c.loo && !c.Validation)
+    if (!c.loo && !c.kfold && !c.Validation)
       die("--K_list needs --Validation true (K is judged on the validation set)");
-    if (!c.loo && c.N_val <= 0) die("--K_list needs a validation set (N_val > 0)");
+    if (!c.loo && !c.kfold && c.N_val <= 0) die("--K_list needs a validation set (N_val > 0)");
     if (c.K_list.size() > 4096) die("--K_list takes at most 4096 values");
     for (size_t i = 0; i < c.K_list.size(); i++) {
       if (c.K_list[i] > c.N_train)
@@ -330,6 +348,22 @@ int main(int argc, char** argv) {
       n_groups = std::max(n_groups, groups[(size_t)i] + 1);
     }
   }
+  std::vector<int32_t> folds;  // --kfold: one fold id per train row
+  if (c.kfold) {
+    folds.resize((size_t)c.N_train);
+    if (c.folds_file.empty()) {
+      for (long long i = 0; i < c.N_train; i++) folds[(size_t)i] = (int32_t)(i % c.kfold);
+    } else {
+      std::vector<double> Fv;
+      load(c.folds_file, 1, false, c.N_train, Fv, nullptr, c.threads, gc);
+      for (long long i = 0; i < c.N_train; i++) {
+        const double v = Fv[(size_t)i];
+        if (!(v >= 0.0 && v < (double)c.kfold) || v != (double)(int32_t)v)
+          die(c.folds_file + ": row " + std::to_string(i) + " is not an integer fold id in [0, F)");
+        folds[(size_t)i] = (int32_t)v;
+      }
+    }
+  }
   phase("csv");
   if (gc && c.timings) {
     static const char* const names[5] = {"read", "h2d", "parse", "d2h", "slow"};
@@ -354,7 +388,32 @@ int main(int argc, char** argv) {
   const int metric = c.Euclidean_distance ? KNN_METRIC_L2 : KNN_METRIC_L1;
   const size_t cc = (size_t)c.class_cnt * c.class_cnt;
 
-  if (c.loo) {  // cpp:308-349 with every train row judged against all the others
+  if (c.kfold) {  // cpp:308-349 with every train row judged against the other folds' rows
+    const int32_t nk = (int32_t)c.K_list.size();
+    std::vector<int32_t> pred((size_t)nk * c.N_train);
+    std::vector<int64_t> correct(nk, 0);
+    std::vector<int64_t> conf(c.confusion ? nk * cc : 0, 0), unl(c.confusion ? nk : 0, 0);
+    if (knn_group_set_folds(g, folds.data(), c.kfold)) die(knn_last_error());
+    if (knn_group_kfold_sweep(g, c.K_list.data(), nk, metric, pred.data(), correct.data(),
+                              c.confusion ? conf.data() : nullptr,
+                              c.confusion ? unl.data() : nullptr))
+      die(knn_last_error());
+    double best = -1.0;
+    int32_t sel = 0;
+    for (int32_t i = 0; i < nk; i++) {
+      double acc = (double)correct[i];  // acc_calc, cpp:69-84
+      acc /= c.N_train;
+      std::cout << "K = " << c.K_list[i] << " kfold accuracy = " << acc << std::endl;
+      if (acc > best) {  // first to strictly exceed, like cpp:332-335
+        best = acc;
+        c.K = c.K_list[i];
+        sel = i;
+      }
+    }
+    std::cout << "selected K = " << c.K << std::endl;
+    if (c.confusion) print_confusion(c.K, c.class_cnt, conf.data() + sel * cc, unl[sel]);
+    phase("kfold");
+  } else if (c.loo) {  // cpp:308-349 with every train row judged against all the others
     const int32_t nk = (int32_t)c.K_list.size();
     std::vector<int32_t> pred((size_t)nk * c.N_train);
     std::vector<int64_t> correct(nk, 0);

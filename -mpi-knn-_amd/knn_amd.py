@@ -50,6 +50,8 @@ EXPORTED = (
     "knn_set_groups", "knn_set_groups_device", "knn_get_group_max",
     "knn_classify_sweep_gexcl_device", "knn_lgo_sweep_device", "knn_lgo_sweep",
     "knn_group_set_groups", "knn_group_lgo_sweep",
+    "knn_set_folds", "knn_get_fold_max", "knn_kfold_sweep_device", "knn_kfold_sweep",
+    "knn_group_set_folds", "knn_group_kfold_sweep",
     "knn_csv_parse_device", "knn_csv_read", "knn_csv_read_device", "knn_csv_last_slow",
     "knn_csv_last_phases",
 )
@@ -189,6 +191,12 @@ def lib():
         "knn_lgo_sweep": ([P, P, i32, i32, P, P, P, P, P, P, P], ctypes.c_int),
         "knn_group_set_groups": ([P, P, i32], ctypes.c_int),
         "knn_group_lgo_sweep": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
+        "knn_set_folds": ([P, P, i32], ctypes.c_int),
+        "knn_get_fold_max": ([P], i32),
+        "knn_kfold_sweep_device": ([P, i32, P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
+        "knn_kfold_sweep": ([P, P, i32, i32, P, P, P, P, P, P, P], ctypes.c_int),
+        "knn_group_set_folds": ([P, P, i32], ctypes.c_int),
+        "knn_group_kfold_sweep": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
         "knn_csv_parse_device": ([P, P, i64, i32, i32, i64, P, P, P, P, i64, P, P], ctypes.c_int),
         "knn_csv_read": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
         "knn_csv_read_device": ([P, ctypes.c_char_p, i32, i32, i64, P, P, P], ctypes.c_int),
@@ -641,6 +649,67 @@ class Classifier:
             out += (idx[:, :kmax], dist[:, :kmax], flags)
         return out
 
+    def set_folds(self, folds, n_folds=None):
+        """Assigns every train row to a fold (int32[n_train], 0 <= id < n_folds,
+        2 <= n_folds <= 64, every fold non-empty; n_folds defaults to max id +
+        1) and builds the fold shards for kfold_sweep (knn_set_folds); None
+        clears them, and so does set_train.  An id out of range raises KnnError
+        naming the row.  Costs one more fp64 copy of the train set on the GPU."""
+        if folds is None:
+            _check(lib().knn_set_folds(self._h, None, 0))
+            return
+        folds = np.ascontiguousarray(folds, dtype=np.int32).reshape(-1)
+        if self.n_train and folds.shape[0] != self.n_train:
+            raise ValueError("folds must have one id per train row")
+        if n_folds is None:
+            n_folds = int(folds.max()) + 1 if folds.size else 1
+        _check(lib().knn_set_folds(self._h, _ptr(folds), int(n_folds)))
+
+    def fold_max(self):
+        """Rows of the largest fold; 0 when no folds are set."""
+        return int(lib().knn_get_fold_max(self._h))
+
+    def kfold_sweep(self, ks, metric=L2, return_neighbors=False, confusion=False, labels=True):
+        """F-fold cross-validated K sweep (knn_kfold_sweep): every train row
+        classified against the rows of all the OTHER folds at every K of `ks`
+        (each <= n_train - fold_max()); correct[i] is the cross-validation
+        count at ks[i].  Returns as lgo_sweep, in train row order."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk, n = ks.shape[0], self.n_train
+        kmax = int(ks.max()) if nk else 0
+        if not labels and not confusion:
+            raise ValueError("labels=False needs confusion=True")
+        C = self.class_cnt
+        out_lab = np.empty((nk, n), np.int32) if labels else None
+        correct = np.zeros(nk, np.int64)
+        conf = np.zeros((nk, C, C), np.int64) if confusion else None
+        unl = np.zeros(nk, np.int64) if confusion else None
+        flags = np.empty(n, np.int32) if return_neighbors else None
+        idx = np.empty((n, max(kmax, 1)), np.int64) if return_neighbors else None
+        dist = np.empty((n, max(kmax, 1)), np.float64) if return_neighbors else None
+        if idx is not None and kmax == 0:
+            idx = dist = None
+        _check(lib().knn_kfold_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(out_lab),
+                                     _ptr(correct), _ptr(conf), _ptr(unl), _ptr(idx), _ptr(dist),
+                                     _ptr(flags)))
+        out = (out_lab, correct) if labels else (correct,)
+        if confusion:
+            out += (conf, unl)
+        if return_neighbors:
+            if idx is None:
+                idx, dist = np.empty((n, 0), np.int64), np.empty((n, 0), np.float64)
+            out += (idx[:, :kmax], dist[:, :kmax], flags)
+        return out
+
+    def kfold_sweep_device(self, fold, ks, metric, d_labels, d_correct=None, d_idx=None,
+                           d_dist=None, d_flags=None, stream=None):
+        """The sweep of one fold's rows, in the fold's ascending row order, into
+        device buffers (enqueue only): d_labels [nk][n_f], d_correct [nk]."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        _check(lib().knn_kfold_sweep_device(self._h, int(fold), _ptr(ks), ks.shape[0],
+                                            int(metric), d_labels, d_correct, d_idx, d_dist,
+                                            d_flags, stream))
+
     def lgo_sweep_device(self, row0, rows, ks, metric, d_labels, d_correct=None, d_idx=None,
                          d_dist=None, d_flags=None, stream=None):
         """Leave-group-out sweep of train rows [row0, row0 + rows) into device
@@ -1014,6 +1083,37 @@ class Group:
                                          _ptr(correct), _ptr(conf), _ptr(unl)))
         out = (out_lab, correct) if labels else (correct,)
         return out + (conf, unl) if confusion else out
+
+    def set_folds(self, folds, n_folds=None):
+        """Classifier.set_folds on every rank (mode 0; mode 1 raises KnnError)."""
+        if folds is None:
+            _check(lib().knn_group_set_folds(self._h, None, 0))
+            return
+        folds = np.ascontiguousarray(folds, dtype=np.int32).reshape(-1)
+        if self.n_train and folds.shape[0] != self.n_train:
+            raise ValueError("folds must have one id per train row")
+        if n_folds is None:
+            n_folds = int(folds.max()) + 1 if folds.size else 1
+        _check(lib().knn_group_set_folds(self._h, _ptr(folds), int(n_folds)))
+
+    def kfold_sweep(self, ks, metric=L2, confusion=False, labels=True):
+        """Classifier.kfold_sweep over the group (mode 0; mode 1 raises
+        KnnError): rank r sweeps folds r, r + G, ...; returns as lgo_sweep."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        nk, n = ks.shape[0], self.n_train
+        if not labels and not confusion:
+            raise ValueError("labels=False needs confusion=True")
+        C = self.class_cnt
+        out_lab = np.empty((nk, n), np.int32) if labels else None
+        correct = np.zeros(nk, np.int64)
+        conf = np.zeros((nk, C, C), np.int64) if confusion else None
+        unl = np.zeros(nk, np.int64) if confusion else None
+        _check(lib().knn_group_kfold_sweep(self._h, _ptr(ks), nk, int(metric), _ptr(out_lab),
+                                           _ptr(correct), _ptr(conf), _ptr(unl)))
+        out = (out_lab, correct) if labels else (correct,)
+        if confusion:
+            out += (conf, unl)
+        return out
 
     def last_compute_seconds(self):
         return float(lib().knn_group_last_compute_seconds(self._h))

@@ -323,9 +323,10 @@ int knn_loo_sweep_eval(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metr
  * differ.  gq = -1, or any gq outside [0, n_groups), excludes nothing: that
  * query equals the plain sweep's.  KNN_VOTE_DISTANCE applies as in every sweep.
  * One search at max(ks) + gmax serves a call (gmax: the largest group's
- * size): large groups are served correctly, but through that wide search --
- * masking the group inside the candidate pass (k-fold with folds of thousands
- * of rows) is not done here.
+ * size): large groups are served correctly, but through that wide search.
+ * K-fold cross-validation (folds of thousands of rows) has a route of its own
+ * that masks nothing inside the candidate pass: knn_set_folds / knn_kfold_sweep
+ * below, on fold shards.
  *
  * knn_set_groups / knn_set_groups_device attach the ids to the current train
  * set (local rows, [n_train]); the host variant copies them, the device
@@ -364,6 +365,71 @@ int knn_lgo_sweep_device(knn_ctx* ctx, int64_t row0, int64_t rows, const int32_t
 int knn_lgo_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric, int32_t* out_labels,
                   int64_t* out_correct, int64_t* out_conf, int64_t* out_unl, int64_t* out_idx,
                   double* out_dist, int32_t* out_flags);
+
+/* ---- F-fold cross-validated K sweep on fold shards.  The standard way to
+ * choose K: folds[n] (int32, 0 <= id < n_folds) assigns every train row to a
+ * fold, and each row is classified against the rows of all the OTHER folds.
+ * One rule fixes every output: for train row r with f = folds[r] the result is
+ * what knn_classify_sweep returns for query X[r] on a context whose train set
+ * is the current one WITH EVERY ROW OF FOLD f REMOVED (labels lose the same
+ * entries), reported indices mapped back to the full train set -- the rule of
+ * knn_lgo_sweep with groups = folds.  It covers the label at every K, idx and
+ * its order, dist, KNN_FLAG_TIE_BOUNDARY | TIE_VOTE | TIE_ORDER | TIE_REF and
+ * the rows "ties" = 0 / 1 / 2 re-order: the order among equal distances is the
+ * reference's std::sort over the n - n_f remaining records in row order
+ * (cpp:323).  KNN_FLAG_EXACT_RESCAN is outside the contract.
+ * KNN_VOTE_DISTANCE applies as in every sweep.
+ * How: nothing is masked inside a candidate kernel (that would compute all n^2
+ * pairs and discard 1 / F of them).  knn_set_folds gathers the train set
+ * stably, fold by fold, into one fold-major fp64 copy and makes every fold's
+ * slice the train set of an internal sub-context on the same device
+ * (knn_set_train_device; the parent's precision and tuning keys are forwarded,
+ * at knn_set_folds and again at every sweep; the vote mode stays with the
+ * parent).  Fold f's rows are then searched in the other F - 1 shards
+ * (knn_search_partial_device at w = kmax + 1, shards below w rows padded), the
+ * lists' local indices are rewritten to original rows -- the gather is stable,
+ * so every list stays sorted by (dist, idx) -- and merged at kmax as
+ * knn_merge_vote_device does; the sweep tie scan queues the queries whose label
+ * at some K the reference's order could change, and those (rare) are re-ordered
+ * by the leave-group-out reference-order pass over the parent's rows with the
+ * fold as the group (queue and pass are sized on the device: no host wait);
+ * the prefix votes read the parent's labels.  (F - 1) / F n^2 pairs in all.
+ * Memory: one extra fp64 copy of the train set (n x d x 8 B, plus labels and
+ * two int32 per row) and the folds' candidate images, which add up to one
+ * more set of the images a context builds.
+ * knn_last_candidate_path / knn_last_kernel_name of the context report the
+ * last shard search of the last k-fold call.
+ *
+ * knn_set_folds: folds is a host array [n_train]; 2 <= n_folds <= 64 and every
+ * fold non-empty (KNN_ERR_ARG, naming the empty fold); an id outside [0,
+ * n_folds) is KNN_ERR_ARG naming the first such row (set_groups' check and
+ * histogram kernel) -- no folds are set then.  KNN_ERR_STATE before a train set
+ * exists.  NULL clears the folds, and so does every knn_set_train*.  The call
+ * waits, as set_train does.  Independent of knn_set_groups: both may be set.
+ * knn_get_fold_max: the largest fold's size, 0 when no folds are set. */
+int knn_set_folds(knn_ctx* ctx, const int32_t* folds, int32_t n_folds);
+int32_t knn_get_fold_max(knn_ctx* ctx);
+/* The sweep of one fold's rows into device buffers, in the fold's ascending
+ * original-row order (n_f rows): d_labels [nk][n_f] required; d_correct [nk]
+ * (nullable, zeroed by the call: #{rows whose label at ks[i] is their own});
+ * d_idx / d_dist [n_f * kmax], d_flags [n_f] nullable.  0 <= ks[i] <= n_train -
+ * fold_max (KNN_ERR_ARG names the offending entry); KNN_ERR_STATE without
+ * folds; KNN_ERR_ARG for a fold outside [0, n_folds).  Works in batches of at
+ * most 16384 rows; enqueue only, on the stream on_stream (NULL: the context's
+ * own), like its siblings -- the sub-contexts' work included. */
+int knn_kfold_sweep_device(knn_ctx* ctx, int32_t fold, const int32_t* ks, int32_t nk,
+                           int32_t metric, int32_t* d_labels, int64_t* d_correct, int64_t* d_idx,
+                           double* d_dist, int32_t* d_flags, void* on_stream);
+/* Host twin over every fold (waits for the result), outputs in TRAIN ROW order:
+ * out_labels [nk][n] (nullable when out_conf is given), out_correct [nk] (the
+ * F-fold cross-validation count at ks[i], summed over all rows), out_conf
+ * [nk*C*C] and out_unl [nk] (summed over the batches on the device,
+ * knn_confusion_device's convention), out_idx / out_dist [n*kmax], out_flags
+ * [n]: each nullable.  Batches of at most 16384 rows of one fold, so the
+ * workspace does not grow with n. */
+int knn_kfold_sweep(knn_ctx* ctx, const int32_t* ks, int32_t nk, int32_t metric,
+                    int32_t* out_labels, int64_t* out_correct, int64_t* out_conf, int64_t* out_unl,
+                    int64_t* out_idx, double* out_dist, int32_t* out_flags);
 
 /* ---- distance-weighted voting: the second hyperparameter of a KNN classifier.
  * The vote mode is state of the context, like the precision:
@@ -801,6 +867,18 @@ int knn_group_set_groups(knn_group* g, const int32_t* groups, int32_t n_groups);
 int knn_group_lgo_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
                         int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
                         int64_t* out_unl);
+/* K-fold sweep over the group (see knn_set_folds and knn_kfold_sweep), mode 0
+ * only.  knn_group_set_folds: folds [n] (host; NULL clears) go to every rank's
+ * copy of the train set, each rank builds the fold shards on its GPU;
+ * knn_group_set_train clears them.  knn_group_kfold_sweep: rank r sweeps folds
+ * r, r + G, ... (a host thread per rank); out_labels [nk][n] in train row order
+ * (nullable when out_conf is given), out_correct, out_conf [nk*C*C], out_unl
+ * [nk] nullable, summed over the ranks on the host.  mode 1 (train-sharded):
+ * not served by either call, KNN_ERR_ARG with a message saying so. */
+int knn_group_set_folds(knn_group* g, const int32_t* folds, int32_t n_folds);
+int knn_group_kfold_sweep(knn_group* g, const int32_t* ks, int32_t nk, int32_t metric,
+                          int32_t* out_labels, int64_t* out_correct, int64_t* out_conf,
+                          int64_t* out_unl);
 /* Seconds of the last group classify spent between the first enqueue and
  * the last device completion (device-resident inputs, excludes H2D/D2H). */
 double knn_group_last_compute_seconds(knn_group* g);
