@@ -45,6 +45,14 @@ constexpr int fix16_wide_round(int DP) { return DP <= 256 ? 0 : DP <= 512 ? 1 : 
 // slab up to 64 chunks (512 dims), two halves above; chunks of the first slab
 constexpr int fix16_wide_slab0(int cpr) { return cpr > 64 ? (cpr + 1) / 2 : cpr; }
 
+// Queries per pass of the fast rescan's filter above 256 dims
+// (rescan_filter_wide_kernel, knn_select.hip) at padded width DP: the largest
+// of 8, 4, 2, 1 whose rows and thresholds, FQW (DP + 1) floats, fit lds_limit
+// bytes beside the kernel's own variables (8 FQW + 8 bytes; 128 reserved); 0
+// where not even one query fits (no filter then: the full scan takes every
+// failed query)
+int rescan_wide_queries(int DP, int64_t lds_limit);
+
 #define KNN_DP_LIST(X) X(8) X(16) X(24) X(32) X(48) X(64) X(96) X(128) X(160) X(192) X(256)
 
 }  // namespace knnk

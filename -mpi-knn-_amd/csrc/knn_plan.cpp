@@ -78,6 +78,14 @@ int pad_dim_fp16_s3(int d) {
   return DP > 256 ? DP : -1;
 }
 
+// the wide rescan filter's queries per pass (knn_dims.h): on a gfx950 CU
+// (160 KiB) 8 up to DP = 5088, 4 up to 10208, 2 up to 20448, 1 up to 40896
+int rescan_wide_queries(int DP, int64_t lds_limit) {
+  for (int fqw : {8, 4, 2, 1})
+    if ((int64_t)fqw * (DP + 1) * 4 + 128 <= lds_limit) return fqw;
+  return 0;
+}
+
 // the S3 grouping (s3_map) that n_qt and S admit, the largest up to gq_max
 // (a row chunk then serves gq workgroups of the XCD, a query chunk 32 / gq):
 // 32, 16, 8, 4, 2, 1, else 0

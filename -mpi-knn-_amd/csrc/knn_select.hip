@@ -3,6 +3,7 @@
 #include "knn_device.h"
 
 #include <algorithm>
+#include <atomic>
 
 // Timing-only experiment builds (tools: a variant library): the merge kernel
 // returns after stage N (1 loads + error bound, 2 + selection, 3 + exact
@@ -183,9 +184,28 @@ __device__ void rescan_prep_query(const RescanPrep& t, int d, const double* __re
 //     differences, then each thread adds its candidate's terms in dimension
 //     order -- bit-exact with cpp:33-50 / cpp:51-67 (sequential, no FMA).
 //  3. sort (dist, idx), certify LB + ||q'||^2 - E > d_W^2, vote / output.
-// Dynamic LDS: qv[d] f64 (d <= kMergeLdsDim) | dk[C2] f64 | tb[NT][17] f64 |
-// di[C2] | ls[C2].
+// Dynamic LDS: qv[d] f64 (q_lds: d <= kMergeLdsDim and the block still fits
+// the device's LDS, launch_mr) | dk[C2] f64 | tb[NT][17] f64 | di[C2] | ls[C2].
+// At d = 4096 with the largest candidate set (C2 = 1024, NT = 256) that is
+// 32 + 8 + 34 + 8 = 82 KiB.
 constexpr int kMergeLdsDim = 4096;
+constexpr size_t kMergeStaticLds = 2048;  // >= the kernel's own __shared__ variables
+
+// The LDS one workgroup may ask for on the current device (from its
+// properties, read once per device).
+static size_t device_lds_limit() {
+  static std::atomic<int> lim[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  int v = lim[dev].load(std::memory_order_relaxed);
+  if (v <= 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+        v <= 0)
+      v = 64 * 1024;
+    lim[dev].store(v, std::memory_order_relaxed);
+  }
+  return (size_t)v;
+}
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                    __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
@@ -358,7 +378,7 @@ merge_rerank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, in
                     TrainDev t, const double* __restrict__ Q64, int W, int Cmax, int C2,
                     double f_err, ProxyScale ps, const uint32_t* __restrict__ gthr, Sink sink,
                     int* __restrict__ rescan_q, double* __restrict__ rescan_tau,
-                    int* __restrict__ rescan_cnt, SplitMap sm, RescanPrep rp) {
+                    int* __restrict__ rescan_cnt, SplitMap sm, RescanPrep rp, int q_lds) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int s_cn, s_cert, s_f;
   __shared__ double s_lb, s_lbr, s_qa, s_e, s_pinv;
@@ -369,7 +389,7 @@ merge_rerank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, in
   __shared__ uint32_t s_bs[64];  // per split: min over its full lists' R-th entries (keys)
   const int d = t.d;
   // the query row is staged in LDS up to kMergeLdsDim dims, else read in place
-  const bool q_in_lds = d <= kMergeLdsDim;
+  const bool q_in_lds = q_lds != 0;
   double* dk = (double*)smem + (q_in_lds ? d : 0);
   double* tb = dk + C2;
   // (exact_sorted stages at most min(NT, C2) rows per batch: cn <= C2)
@@ -781,11 +801,14 @@ static void launch_mr(const float* cv, const int* ci, int U, int R, const TrainD
                       const RescanPrep& rp, hipStream_t s) {
   // (the staging tile only as large as the candidate set: a smaller
   // footprint keeps more of these latency-bound workgroups per CU)
-  const size_t lds = (size_t)(t.d <= kMergeLdsDim ? t.d : 0) * 8 + (size_t)C2 * 8 +
-                     (size_t)std::min(NT, C2) * 17 * 8 + (size_t)C2 * 8;
+  const size_t work = (size_t)C2 * 8 + (size_t)std::min(NT, C2) * 17 * 8 + (size_t)C2 * 8;
+  // the query row beside it where the device's LDS holds both (82 KiB at most)
+  const int q_lds = t.d <= kMergeLdsDim &&
+                    work + (size_t)t.d * 8 + kMergeStaticLds <= device_lds_limit();
+  const size_t lds = work + (q_lds ? (size_t)t.d * 8 : 0);
   hipLaunchKernelGGL((merge_rerank_kernel<METRIC, NT, EPL, EPT>), dim3((unsigned)m), dim3(NT), lds, s,
                      cv, ci, U, R, t, Q64, W, Cmax, C2, f_err, ps, gthr, sink, rescan_q, rescan_tau,
-                     rescan_cnt, sm, rp);
+                     rescan_cnt, sm, rp, q_lds);
 }
 
 void launch_merge_rerank(int metric, const float* cv, const int* ci, int NL, int R,
@@ -1436,16 +1459,30 @@ void launch_rescan(int metric, const TrainDev& t, const double* Q64, const Resca
     } else {
       // 64 rows per 4-wave block; 8 queries per pass (a failed query is rare
       // at d > 256: the LDS of 8 query rows leaves room for 5 blocks per CU,
-      // i.e. more row loads in flight than 2 blocks with 16 queries)
-      constexpr int FQW = 8;
-      const size_t qbw = (size_t)FQW * (t.DP + 1) * 4;
+      // i.e. more row loads in flight than 2 blocks with 16 queries).  Their
+      // rows take FQW (DP + 1) floats of LDS: 64 KiB at DP = 2047, and beyond
+      // the 160 KiB of a gfx950 CU from DP = 5120, so the queries per pass
+      // halve until the block fits the device's limit -- 8 up to DP = 5088, 4
+      // up to 10208, 2 up to 20448, 1 up to 40896 there (rescan_wide_queries, knn_plan.cpp).
       const dim3 fg((unsigned)std::min<int64_t>((t.n_pad + 63) / 64, 4096));
-      if (metric == 0)
-        hipLaunchKernelGGL((rescan_filter_wide_kernel<0, FQW>), fg, dim3(256), qbw, s, t, rb.qf,
-                           rb.thr, rb.cnt, cap, rb.fcnt, rb.buf, mk, mS, mT);
-      else
-        hipLaunchKernelGGL((rescan_filter_wide_kernel<1, FQW>), fg, dim3(256), qbw, s, t, rb.qf,
-                           rb.thr, rb.cnt, cap, rb.fcnt, rb.buf, mk, mS, mT);
+      const int fqw = rescan_wide_queries(t.DP, (int64_t)device_lds_limit());
+      const size_t qbw = (size_t)fqw * (t.DP + 1) * 4;
+#define KNN_FW(M_, F_) \
+  hipLaunchKernelGGL((rescan_filter_wide_kernel<M_, F_>), fg, dim3(256), qbw, s, t, rb.qf, rb.thr, \
+                     rb.cnt, cap, rb.fcnt, rb.buf, mk, mS, mT)
+      if (metric == 0) {
+        if (fqw == 8) KNN_FW(0, 8); else if (fqw == 4) KNN_FW(0, 4);
+        else if (fqw == 2) KNN_FW(0, 2); else if (fqw == 1) KNN_FW(0, 1);
+      } else {
+        if (fqw == 8) KNN_FW(1, 8); else if (fqw == 4) KNN_FW(1, 4);
+        else if (fqw == 2) KNN_FW(1, 2); else if (fqw == 1) KNN_FW(1, 1);
+      }
+#undef KNN_FW
+      // not even one query row fits: no filter runs, and every failed query
+      // must take the full scan.  The merge left fcnt at the rows it handed
+      // over (possibly >= W of them); a count beyond kRescanCap is the value
+      // rescan_finish_fast_kernel passes on.
+      if (fqw == 0) launch_fill_i32(rb.fcnt, cap, kRescanCap + 1, s);
     }
     const size_t lds = (size_t)(t.d <= 1024 ? t.d : 0) * 8 + (size_t)kRescanCap * 8 +
                        (size_t)256 * 17 * 8 + (size_t)kRescanCap * 8;

@@ -108,10 +108,13 @@ def assert_neighbors_match(idx, dist, widx, wdist, flags=None, labels_msg=""):
 TIE_VOTES = {"cases": 0, "queries": 0, "tie_vote": 0, "tie_vote_label_differs": 0, "where": []}
 
 
-def run_case(clf, knn, train, lab, queries, k, metric, classes):
+def run_case(clf, knn, train, lab, queries, k, metric, classes, want=None):
+    """`want`: the oracle's (labels, idx, dist) at n_out = k where the caller
+    already has them (one oracle run shared by several configurations)."""
     clf.set_train(train, lab, classes)
     got, idx, dist, flags = clf.classify(queries, k, metric, return_neighbors=True)
-    want, widx, wdist = oracle.knn(train, lab, queries, k, metric == 0, classes, n_out=k)
+    want, widx, wdist = want if want is not None else oracle.knn(
+        train, lab, queries, k, metric == 0, classes, n_out=k)
     tie_vote = (flags & knn.FLAG_TIE_VOTE) != 0
     assert (got[~tie_vote] == want[~tie_vote]).all(), "labels differ on untied queries"
     differs = int((got[tie_vote] != want[tie_vote]).sum())

@@ -9,6 +9,7 @@
 //   make -C -mpi-knn-_amd bin/plan_check && -mpi-knn-_amd/bin/plan_check
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <vector>
@@ -32,7 +33,8 @@ int fake_trows(int metric, int DP) {
   if (metric == 7) return DP > 128 ? 64 : 128;
   return DP <= 256 ? g_trows : 128;
 }
-bool fake_qres(int DP) { return DP % 64 == 0; }
+// (no build has had a query-resident kernel beyond 30 chunks, DP = 960)
+bool fake_qres(int DP) { return DP % 64 == 0 && DP <= 960; }
 const KernelFacts kFake = {fake_blocks, fake_s3q_blocks, fake_qpw, fake_trows, fake_qres};
 
 long g_plans = 0, g_named = 0, g_bad = 0;
@@ -131,25 +133,64 @@ void check(const Shape& sh, const Tuning& tune, const char* tkey, int64_t tval) 
     REQUIRE(tune.i8l1 != 2 || !sh.i8_ok || sh.d > 1024);
   }
   REQUIRE((pad_dim_i8l1w(sh.d) > 0) == (sh.d > 256 && sh.d <= 1024));
+  // Above 1024 dims no code pass applies (the wide L1 passes hand over to the
+  // fp32 L1 stream kernel whatever "i8l1" and "u16l1w" say), no int8 pass, no
+  // query-resident kernel; the widths pad to the stream kernels' granules and
+  // each precision names its stream kernel.
+  if (sh.d > 1024) {
+    const int d32 = (sh.d + 31) / 32 * 32, d16 = (sh.d + 15) / 16 * 16;
+    REQUIRE(pad_dim(sh.d) == d32 && pad_dim_fp16_s3(sh.d) == d32 && pad_dim_bf16x3(sh.d) == d16);
+    REQUIRE(pad_dim_i8l1w(sh.d) < 0 && pad_dim_u16l1w(sh.d) < 0 && pad_dim_fp16(sh.d) < 0);
+    REQUIRE(pad_dim_i8(sh.d) < 0 && pad_dim_i8w(sh.d) < 0);
+    REQUIRE(!p.qres && p.kmetric != 5 && p.kmetric != 6 && p.kmetric != 7 && p.kmetric != 8);
+    REQUIRE(p.R == 8 || p.R == 16);
+    char want[64];
+    if (sh.metric == KNN_METRIC_L1) {
+      REQUIRE(p.kmetric == 1 && p.DP == d32 && p.image == IMG_FP32);
+      snprintf(want, sizeof want, "cand_stream_kernel<32,%d,1>", p.R);
+    } else if (p.kmetric == 4) {
+      REQUIRE(p.s3 && p.s3h && p.DP == d32 && p.image == IMG_FP16_S3 && (!p.s3q || p.R == 8));
+      snprintf(want, sizeof want, "cand_s3_kernel<%d,true,%s>", p.R, p.s3q ? "true" : "false");
+    } else if (p.kmetric == 2) {
+      REQUIRE(p.s3 && !p.s3h && p.DP == d16 && p.image == IMG_BF16X3);
+      snprintf(want, sizeof want, "cand_s3_kernel<%d,false,false>", p.R);
+    } else {
+      REQUIRE(p.kmetric == 0 && p.DP == d32 && p.image == IMG_FP32);
+      snprintf(want, sizeof want, "cand_stream_kernel<32,%d,0>", p.R);
+    }
+    REQUIRE(!strcmp(p.kernel, want));
+    // the fast rescan's wide filter fits a gfx950 CU's 160 KiB at every width
+    // of the grid, with at least 4 queries per pass
+    const int fqw = rescan_wide_queries(pad_dim(sh.d), 160 * 1024);
+    REQUIRE(fqw == (pad_dim(sh.d) <= 5088 ? 8 : 4));
+    REQUIRE((int64_t)fqw * (pad_dim(sh.d) + 1) * 4 + 8 * fqw + 8 <= 160 * 1024);
+  }
 #undef REQUIRE
 }
 
 void walk(const Tuning& tune, const char* tkey, int64_t tval) {
-  static const int ds[] = {1, 16, 24, 96, 128, 256, 257, 288, 300, 320, 784, 960, 1024, 1025};
+  static const int ds[] = {1,    16,   24,   96,   128,  256,  257,  288,  300,  320,  784, 960,
+                           1024, 1025, 1536, 2016, 2048, 3072, 4096, 4097, 5088, 5089, 6000};
   static const int64_t ns[] = {1, 255, 2000, 40000, 1000000, 12500000};
   static const int64_t ms[] = {1, 127, 4095, 4096, 10000, 131072, 1000000};
   // the path's cap: k <= 1000 on this path, W = k + 1 (and never above n)
   static const int Ws[] = {1, 2, 11, 12, 27, 28, 64, 65, 101, 102, 103, 123, 124, 1001};
+  // (beyond 1025 dims nothing in the plan depends on the width but the
+  // padding: a coarser walk over n and m there)
   for (int d : ds)
     for (int64_t n : ns)
       for (int64_t m : ms)
-        for (int W : Ws)
+        for (int W : Ws) {
+          if (d > 1025 && (n == 1 || n == 40000 || n == 12500000 || m == 4095 || m == 10000 ||
+                           m == 1000000))
+            continue;
           for (int metric : {KNN_METRIC_L2, KNN_METRIC_L1})
             for (int prec : {KNN_PRECISION_AUTO, KNN_PRECISION_FP32, KNN_PRECISION_BF16X3,
                              KNN_PRECISION_FP16})
               for (bool i8_ok : {false, true})
                 check(Shape{d, n, m, (int)std::min<int64_t>(W, n), metric, prec, i8_ok}, tune,
                       tkey, tval);
+        }
 }
 
 struct KeyValues {
@@ -160,7 +201,42 @@ struct KeyValues {
 
 }  // namespace
 
-int main() {
+// plan_check pads D...: one line "d pad_dim pad_dim_bf16x3 pad_dim_fp16_s3
+// pad_dim_i8l1w pad_dim_u16l1w rescan_wide_queries(pad_dim, 160 KiB)" per width.
+// plan_check name d n m W metric precision [key=value ...]: the kernel the
+// plan names for one shape (fake facts; a continuous train set).
+int cli(int argc, char** argv) {
+  if (!strcmp(argv[1], "pads")) {
+    for (int i = 2; i < argc; ++i) {
+      const int d = atoi(argv[i]);
+      printf("%d %d %d %d %d %d %d\n", d, pad_dim(d), pad_dim_bf16x3(d), pad_dim_fp16_s3(d),
+             pad_dim_i8l1w(d), pad_dim_u16l1w(d), rescan_wide_queries(pad_dim(d), 160 * 1024));
+    }
+    return 0;
+  }
+  if (!strcmp(argv[1], "name") && argc >= 8) {
+    const Shape sh{atoi(argv[2]), atoll(argv[3]), atoll(argv[4]), atoi(argv[5]), atoi(argv[6]),
+                   atoi(argv[7]), false};
+    Tuning tune;
+    for (int i = 8; i < argc; ++i) {
+      char* eq = strchr(argv[i], '=');
+      const char* err = nullptr;
+      if (!eq) return 2;
+      *eq = 0;
+      if (set_tuning(tune, argv[i], atoll(eq + 1), &err) != KNN_OK) return 2;
+    }
+    const int64_t n_pad = (sh.n + 255) / 256 * 256;
+    const PlanIn in{sh.n, n_pad, sh.d, pad_dim(sh.d), sh.metric, sh.m, sh.W, sh.precision,
+                    false, false, false, 0, false, 256, false, tune, kFake};
+    const SearchPlan p = plan_search(in);
+    printf("%s\n", p.ok ? p.kernel : "-");
+    return 0;
+  }
+  return 2;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return cli(argc, argv);
   // the default tuning under every fake build
   for (int blocks : {1, 2, 3, 4, 8})
     for (int qpw5 : {32, 64})
